@@ -19,7 +19,20 @@ data-path collective, so the timed region needs none.  Default at N > 1:
 --scaling strong, the one C4 problem split across the ranks (BASELINE's C5);
 --scaling weak gives every rank a C4-sized shard of its own (labelled).
 
+A plain run does what the headline figure needs and no more: set-up, warm-up,
+the timed steps, the result line.  --full adds the legs that take runs of
+their own: the BA-iteration wall time (--lm-iters LM iterations on the same
+workload) and, at one GPU, the CPU baselines (oracle port; --no-cpu-baseline
+leaves them out).  --dump-outputs DIR writes what the last timed step left
+for a caller (mi_ba_download_jacobian: block_obs, residuals, jacobian) as
+DIR/<name>.npy, float64; above DUMP_BLOCKS blocks a fixed seeded sample of
+the blocks, the same rows in every run.  The scene is seeded, so the same
+arguments give the same inputs in every run.  (The semantic samples are
+reduced into per-pair blocks on the device by the step and have no download
+entry point: they are not part of the dump.)
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config C4]
+                       [--dump-outputs DIR] [--full]
 """
 import argparse
 import json
@@ -257,6 +270,29 @@ def roofline_semantic(config, ns, avg_ms):
             "samples_per_launch": ns, "avg_launch_ms": avg_ms, "pmc_source": src}
 
 
+# --dump-outputs: at most this many residual blocks are written, and at most
+# 60 MiB (block_obs 8 B + residuals 16 B + jacobian 16 * cols B per block:
+# 200k blocks of OPENCV's 15 columns are 53 MB)
+DUMP_BLOCKS = 200_000
+DUMP_SEED = 0
+
+
+def dump_outputs(ctx, out_dir, rank, world):
+    """What the last linearize() left for a caller, as float64 .npy files: the
+    arrays of mi_ba_download_jacobian, all blocks or a fixed seeded sample of
+    DUMP_BLOCKS of them (sorted block indices; the same rows in every run)."""
+    bo, r, J = ctx.download_jacobian()
+    nb = len(bo)
+    rows = min(nb, DUMP_BLOCKS, (60 << 20) // (8 * (1 + r.shape[1] + J.shape[1] * J.shape[2])))
+    if rows < nb:
+        sel = np.sort(np.random.default_rng(DUMP_SEED).choice(nb, size=rows, replace=False))
+        bo, r, J = bo[sel], r[sel], J[sel]
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in (("block_obs", bo), ("residuals", r), ("jacobian", J)):
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -266,8 +302,14 @@ def main():
     # start in the steady state
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--config", default="C4", choices=sorted(CONFIGS))
-    ap.add_argument("--lm-iters", type=int, default=3, help="LM iterations for the BA-iteration wall time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the BA-iteration wall time (--lm-iters) and, at one GPU, the CPU baselines; "
+                         "a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's downloadable outputs as DIR/<name>.npy")
+    ap.add_argument("--lm-iters", type=int, default=3,
+                    help="LM iterations for the BA-iteration wall time (with --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--lm-solver", default=None, choices=["exact", "iterative"],
                     help="reduced camera system of the BA-iteration figure: exact (dense Schur + Cholesky, "
                          "the 1-GPU default) or iterative (ITERATIVE_SCHUR + SCHUR_JACOBI: one nf-vector "
@@ -340,6 +382,8 @@ def main():
     s_ms, s_n = ctx.kernel_time("semantic_jacobian")
     w_ms, w_n = ctx.kernel_time("input_warm")
     ctx.set_timing(False)
+    if args.dump_outputs:
+        dump_outputs(ctx, args.dump_outputs, rank, world)
     # the linearization context is done: closed before the BA-iteration leg
     # (its idle streams otherwise share the LM context's hardware queues:
     # Cholesky 15.9 vs 14.7 ms, profiles/r4za_ab_cholesky_rest_streams_closed.jsonl)
@@ -349,7 +393,7 @@ def main():
 
     # BA-iteration wall time: a few LM iterations on the same resident context
     lm = None
-    if args.lm_iters > 0:
+    if args.full and args.lm_iters > 0:
         # warm the LM path (lazy code-object loading of every LM kernel and of
         # rocSOLVER) on a small scene of the same model before timing it
         wc = mi_ba.synth_config(cfg["model"], 30, 300, track_length=5, rotation_range=0.05, extra=cfg["extra"])
@@ -447,7 +491,7 @@ def main():
         }
         if lm:
             out.update(lm)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(opts, sc, sem, cfg, nb, ns)
             out["ba_iteration_c2"] = cpu_ba_iteration()
             # the C4 CPU iteration takes ~30 s on the 16-thread share: the committed
