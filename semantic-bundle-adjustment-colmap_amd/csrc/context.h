@@ -112,7 +112,11 @@ struct mi_ba_context {
   bool sem_deferred_box = false;  // "semantic_deferred_box": the deferred pass reads each sample's 3x3 box once
   int sem_prep_early = 0; // "semantic_prep_early": pair tables on the side stream beside the reprojection kernel
                           // (measured slower: 0.823 vs 0.808 ms per step, it slows the warm-up beside it)
-  int sem_dgrid = 24;    // "semantic_deferred_grid": resident deferred-pass workgroups per CU
+  int sem_dgrid = 24;    // "semantic_deferred_grid": resident deferred-pass workgroups per CU (the one-wave
+                         // kernel's default; the four-wave kernel takes it only when set: sem_dgrid_set)
+  bool sem_dgrid_set = false;
+  int sem_dwaves = 4;    // "semantic_deferred_waves": 1 one wave per chunk (semantic_deferred_kernel),
+                         // 4 one wave per stencil parameter group (semantic_deferred_waves_kernel)
   int sem_dvar = 0;      // "semantic_deferred_variant" (tools build): stencil batch / occupancy variants
   int sem_compact = 1;   // "semantic_deferred_compact": the deferred pass over the filled chunks only (resident grid)
   int sem_coarse = 2;    // "semantic_flat_coarse": the flat pass's box from a rotation and a translation group

@@ -2438,6 +2438,12 @@ mi_ba_status mi_ba_set_tuning(mi_ba_context* ctx, const char* key, int32_t value
   }
   if (std::strcmp(key, "semantic_deferred_grid") == 0 && value >= 1 && value <= 64) {
     ctx->sem_dgrid = value;
+    ctx->sem_dgrid_set = true;
+    return MI_BA_OK;
+  }
+  // 1: one wave per 64-sample chunk, 4: one wave per stencil parameter group
+  if (std::strcmp(key, "semantic_deferred_waves") == 0 && (value == 1 || value == 4)) {
+    ctx->sem_dwaves = value;
     return MI_BA_OK;
   }
   if (std::strcmp(key, "semantic_deferred_compact") == 0 && (value == 0 || value == 1)) {

@@ -93,6 +93,7 @@ struct SemanticState {
   DevArray<uint2> dchunks;                 // the chunks the flat pass filled (deferred_compact_kernel), same regions
   DevArray<uint32_t> dcount;               // [model] their number
   int n_cu = 256;                          // compute units (the deferred pass's resident grid)
+  int dwaves_blocks[kNumModels] = {};      // resident four-wave deferred workgroups per CU (occupancy query), per model
   int model_chunks[kNumModels + 1] = {};   // chunk range of each camera model
   // deterministic sums: the flat pass's deferral masks ([tile][4] words),
   // each pair's first tile and first static chunk, the deferred pass's chunk

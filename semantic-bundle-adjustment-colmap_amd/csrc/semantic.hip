@@ -1667,8 +1667,9 @@ __global__ __launch_bounds__(kBlock) void semantic_flat_kernel(SemArgs ak, const
 // Pass 2: chunk = 64 consecutive entries of one pair's deferred region
 // (chunks past the pair's count exit at once).
 // WPE: minimum waves per SIMD asked of the register allocator (tools-build
-// variants; the default build's 128 VGPRs give 4 waves per SIMD, 16 of these
-// 64-thread workgroups per CU)
+// variants; with WPE 1 the compiler reports 126-127 VGPRs, 4 waves per SIMD,
+// 16 of these 64-thread workgroups per CU, and for OPENCV 131 VGPRs, 3 waves
+// per SIMD, 12 per CU)
 template <int M, bool FAST, int NB, bool BOX = false, int WPE = 1>
 __global__ __launch_bounds__(64, WPE) void semantic_deferred_kernel(SemArgs ak, const uint2* __restrict__ chunks,
                                                               const uint32_t* __restrict__ ccount,
@@ -1760,6 +1761,214 @@ __global__ __launch_bounds__(64, WPE) void semantic_deferred_kernel(SemArgs ak, 
     }
   }
   __syncthreads();  // sJ / sbox are rewritten by the next chunk
+  }
+}
+
+// The geometric part of centre_eval (its operation sequence for pw, p2, w,
+// mag, exk) without the raster read: what a stencil group starts from.  The
+// pixel cache stays empty, so a per-point evaluation reads the centre's pixel
+// from the raster like any other (the same value).
+template <int M>
+__device__ __forceinline__ void centre_geometry(const PairConst* __restrict__ P, const SemSample& smp,
+                                                const double* K2, Centre& c) {
+  double rot[3];
+  unit_quat_rotate(P->uqi, smp.pc1, rot);
+  c.pw[0] = rot[0] + P->ti[0];
+  c.pw[1] = rot[1] + P->ti[1];
+  c.pw[2] = rot[2] + P->ti[2];
+  double rot2[3];
+  unit_quat_rotate(P->u2, c.pw, rot2);
+  c.p2[0] = rot2[0] + P->t2[0];
+  c.p2[1] = rot2[1] + P->t2[1];
+  c.p2[2] = rot2[2] + P->t2[2];
+  c.pc.valid = false;
+  c.pc.px = c.pc.py = 0;
+  c.pc.depth = c.pc.label = 0.f;
+  c.st = 0;
+  c.r = 0.0;
+  c.mag = fabs(smp.pc1[0]) + fabs(smp.pc1[1]) + fabs(smp.pc1[2]) + fabs(P->t1[0]) + fabs(P->t1[1]) +
+          fabs(P->t1[2]) + fabs(c.pw[0]) + fabs(c.pw[1]) + fabs(c.pw[2]) + fabs(P->t2[0]) + fabs(P->t2[1]) +
+          fabs(P->t2[2]);
+  c.w[0] = smp.pc1[0] - P->t1[0];
+  c.w[1] = smp.pc1[1] - P->t1[1];
+  c.w[2] = smp.pc1[2] - P->t1[2];
+  c.exk = margin_model_term<M>(K2, c.p2, c.mag);
+}
+
+// One parameter group (GRP: 0 q1, 1 t1, 2 q2, 3 t2) of one sample: the group's
+// three tangent columns by one batched step over all of its parameters, or,
+// when a decision of the step fell inside a margin, by the per-point route for
+// this group alone (stencil_rolled's loop body; a step that clears its margins
+// takes the per-point route's decisions, so the other groups keep theirs).
+// Accumulation as stencil_batched / stencil_rolled.  Returns true when redone.
+template <int M, int GRP>
+__device__ __forceinline__ bool stencil_group(const SemArgs& a, const PairConst* __restrict__ P, const Centre& c,
+                                              const SemSample& smp, const double* K2, const float2* dl2,
+                                              double col[3]) {
+  constexpr int n = (GRP == 0 || GRP == 2) ? 4 : 3;
+  constexpr int m0 = GRP == 0 ? 0 : (GRP == 1 ? 4 : (GRP == 2 ? 7 : 11));
+  const uint32_t mask = GRP == 1 ? P->mask1 : (GRP == 3 ? P->mask2 : 0u);
+  col[0] = col[1] = col[2] = 0.0;
+  // no cached centre pixel: a per-point evaluation that lands on it reads it
+  // from the raster (the same value)
+  const PixelCache none = {0, 0, 0.f, 0.f, false};
+  double fp[4], fm[4];
+  const bool ok = stencil_step<M, true, GRP, 4>(a, P, m0, 0, n, c.w, c.pw, c.p2, c.mag, smp.label1, K2, dl2, 0, c.exk,
+                                                fp, fm);
+  if (ok) {
+#pragma unroll
+    for (int j = 0; j < n; ++j) {
+      const double jm = (fp[j] - fm[j]) * P->ood[m0 + j];
+      if constexpr (GRP == 0 || GRP == 2) {
+        const double* pj = P->pj[(GRP == 0 ? 0 : 4) + j];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) col[q] = col[q] + jm * pj[q];
+      } else {
+        const double v = ((mask >> j) & 1u) ? 0.0 : jm;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) col[q] = q == j ? v : col[q];
+      }
+    }
+    return false;
+  }
+#pragma unroll 1
+  for (int k = 0; k < n; ++k) {
+    const int m = m0 + k;
+    double f2[2] = {0.0, 0.0};
+#pragma unroll 1
+    for (int sg = 0; sg < 2; ++sg) {
+      const double f = stencil_point<M, true, GRP>(a, P, 2 * m + sg, k, c.w, c.pw, c.p2, c.mag, smp.pc1, smp.label1,
+                                                   K2, dl2, none, c.exk);
+      f2[0] = sg == 0 ? f : f2[0];
+      f2[1] = sg == 1 ? f : f2[1];
+    }
+    const double jm = (f2[0] - f2[1]) * P->ood[m];
+    if constexpr (GRP == 0 || GRP == 2) {
+      const double* pj = P->pj[(GRP == 0 ? 0 : 4) + k];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) col[q] = col[q] + jm * pj[q];
+    } else {
+      const double v = ((mask >> k) & 1u) ? 0.0 : jm;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) col[q] = q == k ? v : col[q];
+    }
+  }
+  return true;
+}
+
+// Pass 2, one wave per parameter group ("semantic_deferred_waves" 4): a
+// 256-thread workgroup per chunk, lane tid & 63 the sample, wave tid >> 6 the
+// group (q1, t1, q2, t2).  Each wave holds one group's share of the pair table
+// as scalars and makes one raster round trip (the one-wave kernel keeps all
+// four groups' tables live and runs centre, q1, t1, q2, t2 as five dependent
+// round trips).  The t2 wave, whose points cost least, also evaluates the
+// centre's residual and the corrector scale.  Raw tangent columns meet in LDS;
+// 64 threads then write J and the scaled rows, 90 threads the chunk's sums in
+// row order into the slots the one-wave kernel fills: the values are its
+// values bit for bit.  Barriers only.
+template <int M>
+__global__ __launch_bounds__(256) void semantic_deferred_waves_kernel(SemArgs ak, const uint2* __restrict__ chunks,
+                                                                     const uint32_t* __restrict__ ccount,
+                                                                     const PairConst* __restrict__ pcs,
+                                                                     const uint32_t* __restrict__ pair_cnt,
+                                                                     const uint32_t* __restrict__ dlist,
+                                                                     const uint32_t* __restrict__ pair_chunk0,
+                                                                     double* __restrict__ cpart,
+                                                                     double* __restrict__ J_out, int write_samples,
+                                                                     int32_t* __restrict__ status_out = nullptr) {
+  __shared__ double sraw[64 * 12];      // raw tangent columns, 3 per wave
+  __shared__ double ssc[64], srs[64];   // corrector scale, scaled residual
+  __shared__ double sJ[64 * kSemRow];   // scaled rows
+  __shared__ uint8_t sredo[4 * 64];     // group redone per point (diagnostic)
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint32_t nch = ccount ? *ccount : blockIdx.x + 1;
+  const uint32_t stride = ccount ? gridDim.x : 1u;
+  for (uint32_t ci = blockIdx.x; ci < nch; ci += stride) {
+    const uint2 ch = chunks[ci];  // (pair, first entry)
+    const uint32_t cnt = pair_cnt[ch.x];
+    if (ch.y >= cnt) continue;  // workgroup-uniform
+    const PairConst* __restrict__ P = pcs + ch.x;
+    const SemArgs a = with_pair(ak, P);
+    const uint32_t k = ch.y + lane;
+    const uint32_t pstart = a.pairs[ch.x].start;
+    const float2* dl2 = a.dl + P->roff;
+    const double* K2 = P->K2;
+    double col[3] = {0.0, 0.0, 0.0};
+    bool redone = false;
+    int64_t n = 0;
+    if (k < cnt) {
+      n = (int64_t)pstart + dlist[pstart + k];
+      const SemSample smp = a.samples[n];
+      Centre c;
+      if (wv == 0) {
+        centre_geometry<M>(P, smp, K2, c);
+        if (P->var1) redone = stencil_group<M, 0>(a, P, c, smp, K2, dl2, col);
+      } else if (wv == 1) {
+        centre_geometry<M>(P, smp, K2, c);
+        if (P->var1) redone = stencil_group<M, 1>(a, P, c, smp, K2, dl2, col);
+      } else if (wv == 2) {
+        centre_geometry<M>(P, smp, K2, c);
+        if (P->var2) redone = stencil_group<M, 2>(a, P, c, smp, K2, dl2, col);
+      } else {
+        centre_eval<M, true>(a, P, smp, K2, dl2, c);
+        if (P->var2) redone = stencil_group<M, 3>(a, P, c, smp, K2, dl2, col);
+        double rho[3];
+        loss_eval(a.loss_type, a.loss_scale, c.r * c.r, rho);
+        const double sc = sqrt(a.weight * rho[1]);
+        ssc[lane] = sc;
+        srs[lane] = c.r * sc;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) sraw[lane * 12 + 3 * wv + q] = col[q];
+    sredo[wv * 64 + lane] = redone ? 1 : 0;
+    __syncthreads();
+    if (tid < 64) {
+      double rowv[kSemRow];
+#pragma unroll
+      for (int q = 0; q < kSemRow; ++q) rowv[q] = 0.0;
+      if (k < cnt) {
+        double Jt[12];
+#pragma unroll
+        for (int m = 0; m < 12; ++m) Jt[m] = sraw[lane * 12 + m];
+        if ((write_samples & 4) && status_out && (sredo[lane] | sredo[64 + lane] | sredo[128 + lane] | sredo[192 + lane]))
+          status_out[n] += 0x10000;  // diagnostic
+        if (write_samples) {
+          double2* jo = reinterpret_cast<double2*>(J_out + 12 * n);
+#pragma unroll
+          for (int m = 0; m < 6; ++m) jo[m] = make_double2(Jt[2 * m], Jt[2 * m + 1]);
+        }
+        const double sc = ssc[lane];
+#pragma unroll
+        for (int m = 0; m < 12; ++m) rowv[m] = Jt[m] * sc;
+        rowv[12] = srs[lane];
+      }
+#pragma unroll
+      for (int q = 0; q < kSemRow; ++q) sJ[lane * kSemRow + q] = rowv[q];
+    }
+    __syncthreads();
+    const int rows = min(64, (int)(cnt - ch.y));
+    if (tid < kPairVals) {
+      const int e = tid;
+      int ca, cb;
+      if (e < 78) {
+        int a_ = 0, rem = e;
+        while (rem >= 12 - a_) { rem -= 12 - a_; ++a_; }
+        ca = a_;
+        cb = a_ + rem;
+      } else {
+        ca = e - 78;
+        cb = 12;
+      }
+      double acc = 0.0;
+      for (int q = 0; q < rows; ++q) acc += sJ[q * kSemRow + ca] * sJ[q * kSemRow + cb];
+      // the chunk's J'J / J'r, summed per pair in chunk order (pair_reduce_kernel)
+      cpart[((size_t)pair_chunk0[ch.x] + ch.y / 64) * kPairVals + e] = acc;
+    }
+    // no third barrier: sraw / ssc / srs / sredo are last read before the
+    // second barrier, and the next chunk writes sJ only after its first
+    // barrier, which no thread passes before the sums above are formed
   }
 }
 
@@ -2407,6 +2616,19 @@ mi_ba_status semantic_create(mi_ba_context* ctx, const mi_ba_semantic* sem) {
         ncu <= 0)
       ncu = 256;
     S->n_cu = ncu;
+    // the four-wave deferred kernel's resident workgroups per CU, as the
+    // runtime reports them for each instantiation
+    for (int model = 0; model < kNumModels; ++model) {
+      dispatch_model(model, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, semantic_deferred_waves_kernel<M>, 256, 0) !=
+                hipSuccess ||
+            nb <= 0)
+          nb = 4;
+        S->dwaves_blocks[model] = nb;
+      });
+    }
   }
   if (!chunks.empty() && hipMemcpy(S->chunks.ptr, chunks.data(), chunks.size() * sizeof(uint2), hipMemcpyHostToDevice))
     return MI_BA_ERR_HIP;
@@ -2626,16 +2848,35 @@ mi_ba_status semantic_linearize(mi_ba_context* ctx, double* d_cost, bool write_s
       for (int model = 0; model < kNumModels; ++model) {
         const int c0 = S->model_chunks[model], nc = S->model_chunks[model + 1] - c0;
         if (S->model_tiles[model + 1] == S->model_tiles[model] || nc == 0) continue;
-        // compact: a grid of 64-thread workgroups, semantic_deferred_grid per CU
-        // (16 resident at 128 VGPRs, LDS would allow 24 at 6.6 KB each; 24
-        // measured 6 us faster than 16: the extra ones take the second round's
-        // chunks as the first finish); else one per static chunk
-        const int grid = compact ? std::min(nc, std::max(1, ctx->sem_dgrid) * S->n_cu) : nc;
+        // compact: a resident grid looping over the filled chunks; else one
+        // workgroup per static chunk.  One-wave kernel: 64-thread workgroups,
+        // semantic_deferred_grid per CU.  Its registers (131 VGPRs for OPENCV:
+        // 3 waves per SIMD, 12 resident per CU; 126-127 for the other models:
+        // 4 per SIMD, 16 per CU) hold fewer than the default 24, which
+        // measured 6 us faster than 16: the extra ones take the next round's
+        // chunks as the first finish.  Four-wave kernel: 256-thread
+        // workgroups, as many per CU as the runtime's occupancy query reports
+        // (one wave of a workgroup per SIMD; the compiler reports 100 VGPRs,
+        // 4 waves per SIMD for OPENCV: 4 workgroups per CU; 89-93 VGPRs, 5
+        // waves per SIMD for the other models: 5 per CU), or
+        // semantic_deferred_grid when set.
+        const bool waves4 = ctx->sem_dwaves == 4 && !ctx->sem_deferred_box
+#ifdef MI_BA_AB_VARIANTS
+                            && ctx->sem_dvar == 0
+#endif
+            ;
+        const int per_cu = waves4 && !ctx->sem_dgrid_set ? std::max(1, S->dwaves_blocks[model])
+                                                         : std::max(1, ctx->sem_dgrid);
+        const int grid = compact ? std::min(nc, per_cu * S->n_cu) : nc;
         const uint2* list = (compact ? S->dchunks.ptr : S->chunks.ptr) + c0;
         const uint32_t* count = compact ? S->dcount.ptr + model : nullptr;
         dispatch_model(model, [&](auto m) {
           constexpr int M = decltype(m)::value;
-          if (ctx->sem_deferred_box)
+          if (waves4)
+            hipLaunchKernelGGL((semantic_deferred_waves_kernel<M>), dim3(grid), dim3(256), 0, ds, a, list, count,
+                               pcs, S->pair_cnt.ptr, S->dlist.ptr, S->pair_chunk0.ptr, S->cpart.ptr, S->J.ptr, ws,
+                               S->status.ptr);
+          else if (ctx->sem_deferred_box)
             hipLaunchKernelGGL((semantic_deferred_kernel<M, true, 4, true>), dim3(grid), dim3(64), 0, ds, a, list,
                                count, pcs, S->pair_cnt.ptr, S->dlist.ptr, S->pair_chunk0.ptr, S->cpart.ptr, S->J.ptr,
                                ws, S->status.ptr);
