@@ -7,6 +7,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <limits>
 #include <map>
@@ -37,6 +38,22 @@ struct Camera {
   double* ParamsData() { return params.data(); }
   int ModelId() const { return model_id; }
   camera_t CameraId() const { return camera_id; }
+  // Camera::WorldToImage / ImageToWorld (camera.cc): normalized camera
+  // coordinates {u, v} to pixels {x, y} and back, evaluated on the host.  A
+  // model outside the nine supported ones throws std::domain_error, as
+  // camera_models.h:140-141 does.
+  std::array<double, 2> WorldToImage(const std::array<double, 2>& world_point) const {
+    std::array<double, 2> xy{{0, 0}};
+    if (mi_ba_world_to_image(model_id, params.data(), world_point[0], world_point[1], &xy[0], &xy[1]) != MI_BA_OK)
+      throw std::domain_error("Camera model does not exist");
+    return xy;
+  }
+  std::array<double, 2> ImageToWorld(const std::array<double, 2>& image_point) const {
+    std::array<double, 2> uv{{0, 0}};
+    if (mi_ba_image_to_world(model_id, params.data(), image_point[0], image_point[1], &uv[0], &uv[1]) != MI_BA_OK)
+      throw std::domain_error("Camera model does not exist");
+    return uv;
+  }
 };
 
 struct Point2D {

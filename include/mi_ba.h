@@ -70,7 +70,12 @@ enum {
   MI_BA_PINHOLE = 1,
   MI_BA_SIMPLE_RADIAL = 2,
   MI_BA_RADIAL = 3,
-  MI_BA_OPENCV = 4
+  MI_BA_OPENCV = 4,
+  MI_BA_OPENCV_FISHEYE = 5,
+  /* 6 FULL_OPENCV and 10 THIN_PRISM_FISHEYE (12 parameters): unsupported */
+  MI_BA_FOV = 7,
+  MI_BA_SIMPLE_RADIAL_FISHEYE = 8,
+  MI_BA_RADIAL_FISHEYE = 9
 };
 
 /* BundleAdjustmentOptions::LossFunctionType (bundle_adjustment.h:51). */
@@ -315,6 +320,15 @@ int32_t mi_ba_abi_version(void);
 const char* mi_ba_status_string(int32_t status);
 int32_t mi_ba_num_params(int32_t camera_model); /* -1 if unknown */
 mi_ba_status mi_ba_device_count(int32_t* count);
+
+/* --- camera models (host only, no device) --------------------------------- */
+/* Camera::WorldToImage / ImageToWorld: normalized camera coordinates (u, v)
+ * to pixels (x, y) and back, for the nine supported models.
+ * MI_BA_ERR_UNSUPPORTED for any other model id. */
+mi_ba_status mi_ba_world_to_image(int32_t camera_model, const double* params, double u, double v, double* x,
+                                  double* y);
+mi_ba_status mi_ba_image_to_world(int32_t camera_model, const double* params, double x, double y, double* u,
+                                  double* v);
 
 /* --- options ------------------------------------------------------------ */
 void mi_ba_default_options(mi_ba_options* options);

@@ -29,7 +29,7 @@ typedef struct mi_ba_synth_config {
   int32_t track_length;   /* 0 = every point in every image (reference) */
   int32_t image_size;     /* width = height, reference 1000 */
   double focal_factor;    /* f = focal_factor * image_size, reference 1.2 */
-  double extra[4];        /* extra (distortion) params of the model */
+  double extra[4];        /* extra (distortion) params of the model: k / k1 k2 / k1 k2 p1 p2 / k1..k4 (fisheye) / omega (FOV) */
   double rotation_range;  /* axis-angle components ~ U(-r, r); 0 = identity */
   double noise;           /* U(-noise, noise) px, reference 2 */
   uint32_t seed;          /* reference 0 */

@@ -3,7 +3,8 @@
 // Restates, for gfx950 kernels and the host setup, the per-observation math
 // of the reference (AlainSchoebi/semantic-bundle-adjustment-colmap):
 //   camera models   src/base/camera_models.h:545-588, 614-637, 640-690,
-//                   714-757, 760-810, 853-902
+//                   714-757, 760-810, 853-902, 929-986 (OPENCV_FISHEYE),
+//                   1105-1210 (FOV), 1240-1290, 1316-1370 (RADIAL_FISHEYEs)
 //   reprojection    src/base/cost_functions.h:57-81, 116-142
 //   rotations       Ceres 2.1 rotation.h (3rd party, restated) and
 //                   src/util/rotation_extension.h:43-98
@@ -18,18 +19,31 @@
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define MI_HD __host__ __device__ inline
+#define MI_UNROLL _Pragma("unroll")
 #else
 #define MI_HD inline
+#define MI_UNROLL
 #endif
 
 namespace miba {
 
-enum CameraModelId { kSimplePinhole = 0, kPinhole = 1, kSimpleRadial = 2, kRadial = 3, kOpenCV = 4 };
+// COLMAP's kModelId values.  Ids 6 (FULL_OPENCV) and 10 (THIN_PRISM_FISHEYE)
+// have 12 parameters and do not fit the 8-wide camera slot: unsupported.
+enum CameraModelId {
+  kSimplePinhole = 0, kPinhole = 1, kSimpleRadial = 2, kRadial = 3, kOpenCV = 4,
+  kOpenCVFisheye = 5, kFOV = 7, kSimpleRadialFisheye = 8, kRadialFisheye = 9
+};
+// The models of the semantic / GSBA terms (ids 0..4); the reprojection solver
+// also takes the fisheye and FOV models above.
 constexpr int kNumModels = 5;
+MI_HD constexpr bool is_wide_angle_model(int model) {
+  return model == kOpenCVFisheye || model == kFOV || model == kSimpleRadialFisheye || model == kRadialFisheye;
+}
 
 MI_HD int num_params(int model) {
   return model == kSimplePinhole ? 3 : model == kPinhole ? 4 : model == kSimpleRadial ? 4
-       : model == kRadial ? 5 : model == kOpenCV ? 8 : -1;
+       : model == kRadial ? 5 : model == kOpenCV ? 8 : model == kOpenCVFisheye ? 8 : model == kFOV ? 5
+       : model == kSimpleRadialFisheye ? 4 : model == kRadialFisheye ? 5 : -1;
 }
 
 template <int M> struct Model;
@@ -38,11 +52,21 @@ template <> struct Model<kPinhole> { static constexpr int kNumParams = 4; };
 template <> struct Model<kSimpleRadial> { static constexpr int kNumParams = 4; };
 template <> struct Model<kRadial> { static constexpr int kNumParams = 5; };
 template <> struct Model<kOpenCV> { static constexpr int kNumParams = 8; };
+template <> struct Model<kOpenCVFisheye> { static constexpr int kNumParams = 8; };
+template <> struct Model<kFOV> { static constexpr int kNumParams = 5; };
+template <> struct Model<kSimpleRadialFisheye> { static constexpr int kNumParams = 4; };
+template <> struct Model<kRadialFisheye> { static constexpr int kNumParams = 5; };
 // Kernel instantiation for problems whose cameras use different models
 // (camera_models.h:117-141 dispatches per camera): the model is read per
 // camera at run time, parameters are held in 8-wide slots.
 constexpr int kMixedModels = 15;
 template <> struct Model<kMixedModels> { static constexpr int kNumParams = 8; };
+// As kMixedModels for problems in which at least one camera uses a fisheye or
+// FOV model: the run-time switch covers all nine models (switch_model_all).
+// Problems over the five models above keep kMixedModels and its kernels.
+constexpr int kMixedAllModels = 14;
+template <> struct Model<kMixedAllModels> { static constexpr int kNumParams = 8; };
+MI_HD constexpr bool is_mixed(int model) { return model == kMixedModels || model == kMixedAllModels; }
 
 // ---------------------------------------------------------------------------
 // Rotations (Ceres 2.1 rotation.h, restated)
@@ -116,6 +140,62 @@ MI_HD void quat_plus(const double x[4], const double d[3], double out[4]) {
 // ---------------------------------------------------------------------------
 // Camera models: distortion, projection, and their analytic derivatives.
 // ---------------------------------------------------------------------------
+// theta_d of the three fisheye models (extra params k1.. at ex).
+template <int M>
+MI_HD double fisheye_thetad(const double* ex, double theta) {
+  const double theta2 = theta * theta;
+  if constexpr (M == kOpenCVFisheye) {
+    const double theta4 = theta2 * theta2, theta6 = theta4 * theta2, theta8 = theta4 * theta4;
+    return theta * (1.0 + ex[0] * theta2 + ex[1] * theta4 + ex[2] * theta6 + ex[3] * theta8);
+  } else if constexpr (M == kRadialFisheye) {
+    const double theta4 = theta2 * theta2;
+    return theta * (1.0 + ex[0] * theta2 + ex[1] * theta4);
+  } else {
+    return theta * (1.0 + ex[0] * theta2);
+  }
+}
+
+// FOV model: distorted = factor * (u, v).  Three branches, tested in the
+// reference's order with its strict comparisons (omega = 1e-2 squares to
+// exactly 1e-4 in FP64 and so falls through the first test).  dr2 / domega:
+// the derivatives of the branch taken, by radius^2 and by omega.
+constexpr double kFovEpsilon = 1e-4;
+MI_HD double fov_factor(double omega, double radius2) {
+  const double omega2 = omega * omega;
+  if (omega2 < kFovEpsilon) return (omega2 * radius2) / 3.0 - omega2 / 12.0 + 1.0;
+  if (radius2 < kFovEpsilon) {
+    const double t = tan(omega / 2.0);
+    return (-2.0 * t * (4.0 * radius2 * t * t - 3.0)) / (3.0 * omega);
+  }
+  const double radius = sqrt(radius2);
+  return atan(radius * 2.0 * tan(omega / 2.0)) / (radius * omega);
+}
+MI_HD double fov_factor_jac(double omega, double radius2, double* dr2, double* domega) {
+  const double omega2 = omega * omega;
+  if (omega2 < kFovEpsilon) {
+    *dr2 = omega2 / 3.0;
+    *domega = 2.0 * omega * radius2 / 3.0 - omega / 6.0;
+    return (omega2 * radius2) / 3.0 - omega2 / 12.0 + 1.0;
+  }
+  const double t = tan(omega / 2.0);
+  const double dt = 0.5 * (1.0 + t * t);  // d tan(omega/2) / d omega
+  if (radius2 < kFovEpsilon) {
+    const double num = -2.0 * t * (4.0 * radius2 * t * t - 3.0);  // 6 t - 8 radius2 t^3
+    const double factor = num / (3.0 * omega);
+    *dr2 = -8.0 * t * t * t / (3.0 * omega);
+    *domega = ((6.0 - 24.0 * radius2 * t * t) * dt - num / omega) / (3.0 * omega);
+    return factor;
+  }
+  const double radius = sqrt(radius2);
+  const double a = radius * 2.0 * t;
+  const double at = atan(a);
+  const double ia = 1.0 / (1.0 + a * a);
+  const double factor = at / (radius * omega);
+  *dr2 = (2.0 * t * ia * radius - at) / (2.0 * radius2 * radius * omega);
+  *domega = (2.0 * dt * ia - factor) / omega;
+  return factor;
+}
+
 template <int M>
 MI_HD void distortion(const double* ex, double u, double v, double* du, double* dv) {
   if constexpr (M == kSimpleRadial) {
@@ -136,6 +216,22 @@ MI_HD void distortion(const double* ex, double u, double v, double* du, double* 
     const double radial = k1 * r2 + k2 * r2 * r2;
     *du = u * radial + 2.0 * p1 * uv + p2 * (r2 + 2.0 * u2);
     *dv = v * radial + 2.0 * p2 * uv + p1 * (r2 + 2.0 * v2);
+  } else if constexpr (M == kOpenCVFisheye || M == kSimpleRadialFisheye || M == kRadialFisheye) {
+    // equidistant fisheye: theta_d = theta (1 + k1 theta^2 + ...), theta = atan r
+    const double r = sqrt(u * u + v * v);
+    if (r > 2.220446049250313e-16) {
+      const double thetad = fisheye_thetad<M>(ex, atan(r));
+      *du = u * thetad / r - u;
+      *dv = v * thetad / r - v;
+    } else {
+      *du = 0.0;
+      *dv = 0.0;
+    }
+  } else if constexpr (M == kFOV) {
+    // FOVCameraModel::Distortion returns the distorted point, not an offset
+    const double factor = fov_factor(ex[0], u * u + v * v);
+    *du = u * factor;
+    *dv = v * factor;
   } else {
     *du = 0.0;
     *dv = 0.0;
@@ -150,12 +246,17 @@ MI_HD void world_to_image(const double* prm, double u, double v, double* x, doub
   } else if constexpr (M == kPinhole) {
     *x = prm[0] * u + prm[2];
     *y = prm[1] * v + prm[3];
-  } else if constexpr (M == kSimpleRadial || M == kRadial) {
+  } else if constexpr (M == kSimpleRadial || M == kRadial || M == kSimpleRadialFisheye || M == kRadialFisheye) {
     double du, dv;
     distortion<M>(prm + 3, u, v, &du, &dv);
     const double xd = u + du, yd = v + dv;
     *x = prm[0] * xd + prm[1];
     *y = prm[0] * yd + prm[2];
+  } else if constexpr (M == kFOV) {
+    double xd, yd;
+    distortion<M>(prm + 4, u, v, &xd, &yd);
+    *x = prm[0] * xd + prm[2];
+    *y = prm[1] * yd + prm[3];
   } else {
     double du, dv;
     distortion<M>(prm + 4, u, v, &du, &dv);
@@ -213,6 +314,66 @@ MI_HD void world_to_image_jac(const double* prm, double u, double v, double* x, 
     A[3] = f * (1.0 + radial + g * v2);
     Jp[0] = xd; Jp[1] = 1.0; Jp[3] = f * u * r2; Jp[4] = f * u * r2 * r2;
     Jp[np + 0] = yd; Jp[np + 2] = 1.0; Jp[np + 3] = f * v * r2; Jp[np + 4] = f * v * r2 * r2;
+  } else if constexpr (M == kOpenCVFisheye || M == kSimpleRadialFisheye || M == kRadialFisheye) {
+    // (xd, yd) = s (u, v), s = theta_d / r: d s / d(u, v) = g (u, v) with
+    // g = (theta_d' r - theta_d) / r^3, theta_d' = (d theta_d / d theta) / (1 + r^2)
+    constexpr bool two_f = M == kOpenCVFisheye;
+    constexpr int e0 = two_f ? 4 : 3;                   // first extra parameter
+    constexpr int nk = np - e0;                         // k1..k_nk
+    const double fx = prm[0], fy = two_f ? prm[1] : prm[0];
+    const double cx = two_f ? prm[2] : prm[1], cy = two_f ? prm[3] : prm[2];
+    const double r = sqrt(u * u + v * v);
+    if (r > 2.220446049250313e-16) {
+      const double theta = atan(r), theta2 = theta * theta;
+      const double thetad = fisheye_thetad<M>(prm + e0, theta);
+      double dthetad = 1.0, pw = theta2;  // d theta_d / d theta
+MI_UNROLL
+      for (int k = 0; k < nk; ++k) {
+        dthetad += (2 * k + 3) * prm[e0 + k] * pw;
+        pw *= theta2;
+      }
+      const double ir = 1.0 / r;
+      const double s = thetad * ir;
+      const double g = (dthetad / (1.0 + r * r) * r - thetad) * (ir * ir * ir);
+      const double xd = u + (u * thetad / r - u), yd = v + (v * thetad / r - v);
+      *x = fx * xd + cx;
+      *y = fy * yd + cy;
+      A[0] = fx * (s + g * u * u);
+      A[1] = fx * (g * u * v);
+      A[2] = fy * (g * u * v);
+      A[3] = fy * (s + g * v * v);
+      Jp[0] = xd;
+      Jp[np + (two_f ? 1 : 0)] = yd;
+      double tp = theta * theta2 * ir;  // theta^(2k+3) / r
+MI_UNROLL
+      for (int k = 0; k < nk; ++k) {
+        Jp[e0 + k] = fx * u * tp;
+        Jp[np + e0 + k] = fy * v * tp;
+        tp *= theta2;
+      }
+    } else {
+      // the reference's else branch sets the distortion to constants
+      *x = fx * u + cx;
+      *y = fy * v + cy;
+      A[0] = fx; A[1] = 0.0; A[2] = 0.0; A[3] = fy;
+      Jp[0] = u;
+      Jp[np + (two_f ? 1 : 0)] = v;
+    }
+    Jp[two_f ? 2 : 1] = 1.0;
+    Jp[np + (two_f ? 3 : 2)] = 1.0;
+  } else if constexpr (M == kFOV) {
+    const double fx = prm[0], fy = prm[1];
+    double h, fw;
+    const double factor = fov_factor_jac(prm[4], u * u + v * v, &h, &fw);
+    const double xd = u * factor, yd = v * factor;
+    *x = fx * xd + prm[2];
+    *y = fy * yd + prm[3];
+    A[0] = fx * (factor + 2.0 * h * u * u);
+    A[1] = fx * (2.0 * h * u * v);
+    A[2] = fy * (2.0 * h * u * v);
+    A[3] = fy * (factor + 2.0 * h * v * v);
+    Jp[0] = xd; Jp[2] = 1.0; Jp[4] = fx * u * fw;
+    Jp[np + 1] = yd; Jp[np + 3] = 1.0; Jp[np + 4] = fy * v * fw;
   } else {  // OPENCV
     const double fx = prm[0], fy = prm[1], k1 = prm[4], k2 = prm[5], p1 = prm[6], p2 = prm[7];
     const double u2 = u * u, uv = u * v, v2 = v * v, r2 = u2 + v2;
@@ -273,10 +434,25 @@ MI_HD void image_to_world(const double* prm, double x, double y, double* u, doub
   } else if constexpr (M == kPinhole) {
     *u = (x - prm[2]) / prm[0];
     *v = (y - prm[3]) / prm[1];
-  } else if constexpr (M == kSimpleRadial || M == kRadial) {
+  } else if constexpr (M == kSimpleRadial || M == kRadial || M == kSimpleRadialFisheye || M == kRadialFisheye) {
     *u = (x - prm[1]) / prm[0];
     *v = (y - prm[2]) / prm[0];
     iterative_undistortion<M>(prm + 3, u, v);
+  } else if constexpr (M == kFOV) {
+    // FOVCameraModel::Undistortion (closed form)
+    const double uu = (x - prm[2]) / prm[0], vv = (y - prm[3]) / prm[1];
+    const double omega = prm[4], radius2 = uu * uu + vv * vv, omega2 = omega * omega;
+    double factor;
+    if (omega2 < kFovEpsilon) {
+      factor = (omega2 * radius2) / 3.0 - omega2 / 12.0 + 1.0;
+    } else if (radius2 < kFovEpsilon) {
+      factor = (omega * (omega * omega * radius2 + 3.0)) / (6.0 * tan(omega / 2.0));
+    } else {
+      const double radius = sqrt(radius2);
+      factor = tan(radius * omega) / (radius * 2.0 * tan(omega / 2.0));
+    }
+    *u = uu * factor;
+    *v = vv * factor;
   } else {
     *u = (x - prm[2]) / prm[0];
     *v = (y - prm[3]) / prm[1];
@@ -316,6 +492,40 @@ MI_HD void image_to_world_any(int model, const double* prm, double x, double y, 
   switch_model(model, [&](auto m) { image_to_world<decltype(m)::value>(prm, x, y, u, v); });
 }
 
+// The same over all nine models: used only where a camera may carry a fisheye
+// or FOV model, so the five-model paths above keep their code.
+template <typename F>
+MI_HD void switch_model_all(int model, F&& f) {
+  switch (model) {
+    case kSimplePinhole: f(std::integral_constant<int, kSimplePinhole>{}); break;
+    case kPinhole: f(std::integral_constant<int, kPinhole>{}); break;
+    case kSimpleRadial: f(std::integral_constant<int, kSimpleRadial>{}); break;
+    case kRadial: f(std::integral_constant<int, kRadial>{}); break;
+    case kOpenCVFisheye: f(std::integral_constant<int, kOpenCVFisheye>{}); break;
+    case kFOV: f(std::integral_constant<int, kFOV>{}); break;
+    case kSimpleRadialFisheye: f(std::integral_constant<int, kSimpleRadialFisheye>{}); break;
+    case kRadialFisheye: f(std::integral_constant<int, kRadialFisheye>{}); break;
+    default: f(std::integral_constant<int, kOpenCV>{}); break;
+  }
+}
+MI_HD void world_to_image_all(int model, const double* prm, double u, double v, double* x, double* y) {
+  switch_model_all(model, [&](auto m) { world_to_image<decltype(m)::value>(prm, u, v, x, y); });
+}
+MI_HD void world_to_image_jac_all(int model, const double* prm, double u, double v, double* x, double* y,
+                                  double A[4], double Jp8[16]) {
+  switch_model_all(model, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    constexpr int np = Model<M>::kNumParams;
+    double Jp[2 * np];
+    world_to_image_jac<M>(prm, u, v, x, y, A, Jp);
+    for (int rw = 0; rw < 2; ++rw)
+      for (int k = 0; k < 8; ++k) Jp8[rw * 8 + k] = k < np ? Jp[rw * np + k] : 0.0;
+  });
+}
+MI_HD void image_to_world_all(int model, const double* prm, double x, double y, double* u, double* v) {
+  switch_model_all(model, [&](auto m) { image_to_world<decltype(m)::value>(prm, x, y, u, v); });
+}
+
 // Runtime dispatch helpers for host code.
 template <typename F>
 inline void dispatch_model(int model, F&& f) {
@@ -326,6 +536,19 @@ inline void dispatch_model(int model, F&& f) {
     case kRadial: f(std::integral_constant<int, kRadial>{}); break;
     case kOpenCV: f(std::integral_constant<int, kOpenCV>{}); break;
     default: break;
+  }
+}
+// As dispatch_model over all nine models (the reprojection solver, the
+// projection entries and the synthetic generator); the semantic and GSBA
+// terms keep dispatch_model and its five.
+template <typename F>
+inline void dispatch_model_all(int model, F&& f) {
+  switch (model) {
+    case kOpenCVFisheye: f(std::integral_constant<int, kOpenCVFisheye>{}); break;
+    case kFOV: f(std::integral_constant<int, kFOV>{}); break;
+    case kSimpleRadialFisheye: f(std::integral_constant<int, kSimpleRadialFisheye>{}); break;
+    case kRadialFisheye: f(std::integral_constant<int, kRadialFisheye>{}); break;
+    default: dispatch_model(model, f); break;
   }
 }
 

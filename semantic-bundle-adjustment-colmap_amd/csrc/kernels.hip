@@ -114,6 +114,8 @@ __device__ inline double block_cost(const DevProblem& p, const double* __restric
   double x, y;
   if constexpr (M == kMixedModels)
     world_to_image_any(p.cam_model[cam_idx], prm, u, v, &x, &y);
+  else if constexpr (M == kMixedAllModels)
+    world_to_image_all(p.cam_model[cam_idx], prm, u, v, &x, &y);
   else
     world_to_image<M>(prm, u, v, &x, &y);
   const double r0 = x - o.x, r1 = y - o.y;
@@ -132,6 +134,18 @@ __host__ __device__ constexpr unsigned cam_tangent_mask(int M, int RF) {
   if (M == kSimpleRadial) { f = 0x1; pp = 0x6; ex = 0x8; }
   if (M == kRadial) { f = 0x1; pp = 0x6; ex = 0x18; }
   if (M == kOpenCV) { f = 0x3; pp = 0xC; ex = 0xF0; }
+  return ((RF & 1) ? f : 0u) | ((RF & 2) ? pp : 0u) | ((RF & 4) ? ex : 0u);
+}
+// The same over all nine models (camera_models.h: OPENCV_FISHEYE and FOV
+// fx fy cx cy + extras, the RADIAL_FISHEYEs f cx cy + extras).  The run-time
+// callers of the five-model kernels keep cam_tangent_mask.
+__host__ __device__ constexpr unsigned cam_tangent_mask_all(int M, int RF) {
+  unsigned f = 0, pp = 0, ex = 0;
+  if (M == kOpenCVFisheye) { f = 0x3; pp = 0xC; ex = 0xF0; }
+  else if (M == kFOV) { f = 0x3; pp = 0xC; ex = 0x10; }
+  else if (M == kSimpleRadialFisheye) { f = 0x1; pp = 0x6; ex = 0x8; }
+  else if (M == kRadialFisheye) { f = 0x1; pp = 0x6; ex = 0x18; }
+  else return cam_tangent_mask(M, RF);
   return ((RF & 1) ? f : 0u) | ((RF & 2) ? pp : 0u) | ((RF & 4) ? ex : 0u);
 }
 __host__ __device__ constexpr int popcount8(unsigned m) {
@@ -328,15 +342,16 @@ constexpr int kJacPasses = 1;
 [[maybe_unused]] constexpr int kJacR1 = 8 | 16 | 32;  // round-1 production (three serial round trips), A/B variant 23
 // TB: threads per workgroup.  The cost partial is per wave (no workgroup
 // barrier), cost_partial[i / 64].
-// CTX: the camera-slot width of a mixed-model build (M == kMixedModels, RF
-// then unused: the refine flags are applied per camera at run time).
+// CTX: the camera-slot width of a mixed-model build (M == kMixedModels, or
+// kMixedAllModels when a camera uses a fisheye or FOV model; RF then unused:
+// the refine flags are applied per camera at run time).
 template <int M, int RF, int LOSS, int NP, int D = kJacProduction, int WPE = 4, int TB = kBlock, int CTX = 0>
 __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WPE))) void reproj_jacobian_kernel(DevProblem p, double2* __restrict__ r_out,
                                                                  double* __restrict__ J_out,
                                                                  double* __restrict__ cost_partial) {
   constexpr int np = Model<M>::kNumParams;
-  constexpr unsigned CM = cam_tangent_mask(M, RF);
-  constexpr int CT = M == kMixedModels ? CTX : popcount8(CM);
+  constexpr unsigned CM = cam_tangent_mask_all(M, RF);
+  constexpr int CT = is_mixed(M) ? CTX : popcount8(CM);
   constexpr int W = 9 + CT;
   constexpr int W2 = 2 * W;
   unsigned cmask = 0;  // mixed models: the lane's camera's refined-intrinsics mask
@@ -509,6 +524,10 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WPE))) void 
         const int model = (int)((meta >> 16) & 0xffu);
         world_to_image_jac_any(model, prm, u, v, &x, &y, A, Jp);
         cmask = cam_tangent_mask(model, p.refine_mask);
+      } else if constexpr (M == kMixedAllModels) {
+        const int model = (int)((meta >> 16) & 0xffu);
+        world_to_image_jac_all(model, prm, u, v, &x, &y, A, Jp);
+        cmask = cam_tangent_mask_all(model, p.refine_mask);
       } else {
         world_to_image_jac<M>(prm, u, v, &x, &y, A, Jp);
       }
@@ -577,7 +596,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WPE))) void 
     for (int h = 0; h < NP; ++h) {
       if (lane / RP == h && i < p.nb) {
         double* row = slab + (lane % RP) * LS;
-        if constexpr (M == kMixedModels) {
+        if constexpr (is_mixed(M)) {
           emit_row_mixed<CT>(0, row, B, Mq, pose_var, flags, jx, Jp, sc, cv, cmask);
           emit_row_mixed<CT>(1, row + W, B, Mq, pose_var, flags, jx, Jp, sc, cv, cmask);
         } else {
@@ -2319,7 +2338,7 @@ __global__ void grad_max_f_kernel(DevProblem p, const double* __restrict__ g, do
     if (p.cam_var[c]) {
       const double* a = p.cam + 8 * (size_t)c;
       const double* gc = g + 6 * (size_t)p.num_images + (size_t)p.ct * c;
-      const unsigned cm = cam_tangent_mask(p.cam_model[c], p.refine_mask);
+      const unsigned cm = cam_tangent_mask_all(p.cam_model[c], p.refine_mask);
       int t = 0;
       for (int m = 0; m < 8; ++m)
         if ((cm >> m) & 1u) {
@@ -2730,7 +2749,7 @@ __global__ void plus_cameras_kernel(DevProblem p, const double* __restrict__ df,
   // the camera's refined intrinsics, in parameter order, occupy the first
   // slots of its p.ct-wide block (SubsetManifold::Plus)
   const double* d = df + 6 * (size_t)p.num_images + (size_t)p.ct * k;
-  const unsigned cm = cam_tangent_mask(p.cam_model[k], p.refine_mask);
+  const unsigned cm = cam_tangent_mask_all(p.cam_model[k], p.refine_mask);
   int c = 0;
   for (int m = 0; m < 8; ++m)
     if ((cm >> m) & 1u) {
@@ -3593,7 +3612,22 @@ void launch_reproj_jacobian(const DevProblem& p, double2* r, double* J, double* 
     });
     return;
   }
-  dispatch_model(p.model, [&](auto m) {
+  // The nine-model run-time kernel: mixed problems with a fisheye or FOV
+  // camera (single-model problems of those models are compiled per model and
+  // refine mask below, like the other five).
+  if (p.model == kMixedAllModels) {
+    dispatch_ct(p.ct, [&](auto c) {
+      constexpr int CT = decltype(c)::value;
+      if (p.loss_type == kLossTrivial)
+        hipLaunchKernelGGL((reproj_jacobian_kernel<kMixedAllModels, 0, 0, kJacPasses, kJacProduction, 4, kBlock, CT>),
+                           dim3(g), dim3(kBlock), 0, s, p, r, J, cost_partial);
+      else
+        hipLaunchKernelGGL((reproj_jacobian_kernel<kMixedAllModels, 0, 1, kJacPasses, kJacProduction, 4, kBlock, CT>),
+                           dim3(g), dim3(kBlock), 0, s, p, r, J, cost_partial);
+    });
+    return;
+  }
+  dispatch_model_all(p.model, [&](auto m) {
     constexpr int M = decltype(m)::value;
     auto go = [&](auto rf) {
       constexpr int RF = decltype(rf)::value;
@@ -3760,7 +3794,11 @@ void launch_reproj_cost(const DevProblem& p, const double* qt, const double* cam
     hipLaunchKernelGGL(reproj_cost_kernel<kMixedModels>, dim3(g), dim3(kBlock), 0, s, p, qt, cam, X, cost_partial);
     return;
   }
-  dispatch_model(p.model, [&](auto m) {
+  if (p.model == kMixedAllModels) {
+    hipLaunchKernelGGL(reproj_cost_kernel<kMixedAllModels>, dim3(g), dim3(kBlock), 0, s, p, qt, cam, X, cost_partial);
+    return;
+  }
+  dispatch_model_all(p.model, [&](auto m) {
     constexpr int M = decltype(m)::value;
     hipLaunchKernelGGL(reproj_cost_kernel<M>, dim3(g), dim3(kBlock), 0, s, p, qt, cam, X, cost_partial);
   });

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(kTB) void sq_reproj_error_kernel(ProjArgs a, double
 #pragma unroll
   for (int m = 0; m < 8; ++m) prm[m] = a.cam[8 * (size_t)cam + m];
   double x, y;
-  world_to_image_any(a.cam_model[cam], prm, P[0] / P[2], P[1] / P[2], &x, &y);
+  world_to_image_all(a.cam_model[cam], prm, P[0] / P[2], P[1] / P[2], &x, &y);
   const double2 o = a.xy[k];
   out[k] = (x - o.x) * (x - o.x) + (y - o.y) * (y - o.y);
 }

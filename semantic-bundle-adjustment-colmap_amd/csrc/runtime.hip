@@ -74,7 +74,7 @@ double host_block_cost(const mi_ba_options& o, const mi_ba_problem* p, const Hos
   P[0] += t[0]; P[1] += t[1]; P[2] += t[2];
   const double u = P[0] / P[2], v = P[1] / P[2];
   double x = 0, y = 0;
-  world_to_image_any(s.cam_model[cam], prm, u, v, &x, &y);
+  world_to_image_all(s.cam_model[cam], prm, u, v, &x, &y);
   const double r0 = x - p->obs_xy[2 * k], r1 = y - p->obs_xy[2 * k + 1];
   double rho[3];
   loss_eval(o.loss_function_type, o.loss_function_scale, r0 * r0 + r1 * r1, rho);
@@ -1923,6 +1923,24 @@ const char* mi_ba_status_string(int32_t status) {
 
 int32_t mi_ba_num_params(int32_t camera_model) { return num_params(camera_model); }
 
+// Camera::WorldToImage / ImageToWorld (camera.cc, camera_models.h:117-141):
+// host evaluation, no device needed.
+mi_ba_status mi_ba_world_to_image(int32_t camera_model, const double* params, double u, double v, double* x,
+                                  double* y) {
+  if (!params || !x || !y) return MI_BA_ERR_INVALID_ARGUMENT;
+  if (num_params(camera_model) < 0) return MI_BA_ERR_UNSUPPORTED;
+  world_to_image_all(camera_model, params, u, v, x, y);
+  return MI_BA_OK;
+}
+
+mi_ba_status mi_ba_image_to_world(int32_t camera_model, const double* params, double x, double y, double* u,
+                                  double* v) {
+  if (!params || !u || !v) return MI_BA_ERR_INVALID_ARGUMENT;
+  if (num_params(camera_model) < 0) return MI_BA_ERR_UNSUPPORTED;
+  image_to_world_all(camera_model, params, x, y, u, v);
+  return MI_BA_OK;
+}
+
 mi_ba_status mi_ba_device_count(int32_t* count) {
   int n = 0;
   if (!count) return MI_BA_ERR_INVALID_ARGUMENT;
@@ -2646,6 +2664,10 @@ mi_ba_status mi_ba_set_tuning(mi_ba_context* ctx, const char* key, int32_t value
   }
   // PCG product without J reads (the passes recompute the Jacobian rows)
   if (std::strcmp(key, "pcg_matrix_free") == 0 && (value == 0 || value == 1)) {
+    // the matrix-free rows (block_rows_mf) cover the five-model switch only
+    if (value != 0)
+      for (int32_t m : ctx->setup.cam_model)
+        if (is_wide_angle_model(m)) return MI_BA_ERR_UNSUPPORTED;
     ctx->pcg_mf = value != 0;
     if (ctx->pcg_mf) ctx->Jcm.release();
     else {

@@ -2390,6 +2390,11 @@ mi_ba_status semantic_create(mi_ba_context* ctx, const mi_ba_semantic* sem) {
     if (i < 0 || i >= I || j < 0 || j >= I) return MI_BA_ERR_INVALID_ARGUMENT;
     if (i != j && (img_h[i] <= 0 || img_w[i] <= 0 || img_h[j] <= 0 || img_w[j] <= 0))
       return MI_BA_ERR_INVALID_ARGUMENT;
+    // the semantic term covers the five models of kNumModels (the reference's
+    // SBA requires SIMPLE_PINHOLE): a fisheye or FOV camera in a pair is refused
+    if (is_wide_angle_model(ctx->setup.cam_model[p->image_camera[i]]) ||
+        is_wide_angle_model(ctx->setup.cam_model[p->image_camera[j]]))
+      return MI_BA_ERR_UNSUPPORTED;
   }
   auto* S = new SemanticState();
   ctx->sem = S;
@@ -2994,7 +2999,8 @@ void semantic_cost(mi_ba_context* ctx, const double* qt, const double* cam, doub
   if (S->ns == 0) return;
   SemArgs a = make_args(ctx, qt, cam);
   const unsigned g = (unsigned)((S->ns + kBlock - 1) / kBlock);
-  if (ctx->dev.model == kMixedModels) {
+  // is_mixed: sampled pairs only ever hold the five models (semantic_create)
+  if (is_mixed(ctx->dev.model)) {
     hipLaunchKernelGGL(semantic_cost_kernel<kMixedModels>, dim3(g), dim3(kBlock), 0, ctx->stream, a, S->partial.ptr);
   } else {
     dispatch_model(ctx->dev.model, [&](auto m) {

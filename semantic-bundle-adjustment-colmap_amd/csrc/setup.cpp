@@ -18,6 +18,10 @@ void param_groups(int model, std::vector<int>* f, std::vector<int>* pp, std::vec
     case kSimpleRadial: *f = {0}; *pp = {1, 2}; *ex = {3}; break;
     case kRadial: *f = {0}; *pp = {1, 2}; *ex = {3, 4}; break;
     case kOpenCV: *f = {0, 1}; *pp = {2, 3}; *ex = {4, 5, 6, 7}; break;
+    case kOpenCVFisheye: *f = {0, 1}; *pp = {2, 3}; *ex = {4, 5, 6, 7}; break;
+    case kFOV: *f = {0, 1}; *pp = {2, 3}; *ex = {4}; break;
+    case kSimpleRadialFisheye: *f = {0}; *pp = {1, 2}; *ex = {3}; break;
+    case kRadialFisheye: *f = {0}; *pp = {1, 2}; *ex = {3, 4}; break;
     default: break;
   }
 }
@@ -76,7 +80,11 @@ mi_ba_status build_setup(const mi_ba_options& o, mi_ba_problem* p, HostSetup* s)
     if (m != s->cam_model[0]) mixed = true;
     np = std::max(np, num_params(m));
   }
-  s->model = mixed ? kMixedModels : (C > 0 ? s->cam_model[0] : p->camera_model);
+  // a mixed problem with a fisheye or FOV camera takes the nine-model
+  // run-time kernels, every other mixed problem the five-model ones
+  bool wide = false;
+  for (int c = 0; c < C; ++c) wide = wide || is_wide_angle_model(s->cam_model[c]);
+  s->model = mixed ? (wide ? kMixedAllModels : kMixedModels) : (C > 0 ? s->cam_model[0] : p->camera_model);
   s->np = np;
 
   std::vector<int64_t> img_off, img_items, pt_off, pt_items;
@@ -156,9 +164,9 @@ mi_ba_status build_setup(const mi_ba_options& o, mi_ba_problem* p, HostSetup* s)
       }
     return ct;
   };
-  s->ct = tangent(s->model == kMixedModels ? kOpenCV : s->model, s->cam_tan_idx);
+  s->ct = tangent(is_mixed(s->model) ? kOpenCV : s->model, s->cam_tan_idx);
   s->cam_ct.assign(C, 0);
-  if (s->model == kMixedModels) {
+  if (is_mixed(s->model)) {
     s->ct = 0;
     for (int c = 0; c < C; ++c) {
       s->cam_ct[c] = (uint8_t)tangent(s->cam_model[c], nullptr);

@@ -24,6 +24,13 @@ void init_params(int model, double f, double c, const double* extra, double* out
       out[0] = f; out[1] = f; out[2] = c; out[3] = c;
       for (int k = 0; k < 4; ++k) out[4 + k] = extra[k];
       break;
+    case kOpenCVFisheye:  // k1..k4
+      out[0] = f; out[1] = f; out[2] = c; out[3] = c;
+      for (int k = 0; k < 4; ++k) out[4 + k] = extra[k];
+      break;
+    case kFOV: out[0] = f; out[1] = f; out[2] = c; out[3] = c; out[4] = extra[0]; break;  // omega
+    case kSimpleRadialFisheye: out[0] = f; out[1] = c; out[2] = c; out[3] = extra[0]; break;
+    case kRadialFisheye: out[0] = f; out[1] = c; out[2] = c; out[3] = extra[0]; out[4] = extra[1]; break;
     default: break;
   }
 }
@@ -35,7 +42,7 @@ void project(int model, const double* prm, const double* q, const double* t, con
   unit_quat_rotate(qn, X, P);
   P[0] += t[0]; P[1] += t[1]; P[2] += t[2];
   const double u = P[0] / P[2], v = P[1] / P[2];
-  dispatch_model(model, [&](auto m) {
+  dispatch_model_all(model, [&](auto m) {
     constexpr int M = decltype(m)::value;
     world_to_image<M>(prm, u, v, &xy[0], &xy[1]);
   });
@@ -168,7 +175,7 @@ int32_t mi_ba_synth_render(int32_t model, int32_t num_images, const double* came
       for (int y = 0; y < H; ++y)
         for (int x = 0; x < W; ++x) {
           double u = 0, v = 0;
-          dispatch_model(model, [&](auto m) {
+          dispatch_model_all(model, [&](auto m) {
             constexpr int M = decltype(m)::value;
             image_to_world<M>(prm, (double)x, (double)y, &u, &v);
           });

@@ -26,14 +26,18 @@ SYNTH_PATH = os.path.join(_HERE, "libmi_ba_synth.so")
 # status codes / enums (mi_ba.h)
 OK, ERR_INVALID_ARGUMENT, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_HIP, ERR_NO_RESIDUALS, ERR_STATE, ERR_OOM = range(8)
 SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV = range(5)
+# COLMAP ids 6 (FULL_OPENCV) and 10 (THIN_PRISM_FISHEYE) have 12 parameters: unsupported
+OPENCV_FISHEYE, FOV, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE = 5, 7, 8, 9
 LOSS_TRIVIAL, LOSS_SOFT_L1, LOSS_CAUCHY = range(3)
 SOLVER_AUTO, SOLVER_DENSE_SCHUR, SOLVER_ITERATIVE_SCHUR = range(3)
 CONVERGENCE, NO_CONVERGENCE, FAILURE, USER_SUCCESS, USER_FAILURE = range(5)
 SOLVER_CONTINUE, SOLVER_ABORT, SOLVER_TERMINATE_SUCCESSFULLY = range(3)
 CYLINDER_DEFAULT, CYLINDER_BY_2_POINTS = range(2)
 OUT_OF_BOUNDS, INVALID_DEPTH, VALID = -1, -2, 10
-NUM_PARAMS = {SIMPLE_PINHOLE: 3, PINHOLE: 4, SIMPLE_RADIAL: 4, RADIAL: 5, OPENCV: 8}
-MODEL_NAMES = {"SIMPLE_PINHOLE": 0, "PINHOLE": 1, "SIMPLE_RADIAL": 2, "RADIAL": 3, "OPENCV": 4}
+NUM_PARAMS = {SIMPLE_PINHOLE: 3, PINHOLE: 4, SIMPLE_RADIAL: 4, RADIAL: 5, OPENCV: 8,
+              OPENCV_FISHEYE: 8, FOV: 5, SIMPLE_RADIAL_FISHEYE: 4, RADIAL_FISHEYE: 5}
+MODEL_NAMES = {"SIMPLE_PINHOLE": 0, "PINHOLE": 1, "SIMPLE_RADIAL": 2, "RADIAL": 3, "OPENCV": 4,
+               "OPENCV_FISHEYE": 5, "FOV": 7, "SIMPLE_RADIAL_FISHEYE": 8, "RADIAL_FISHEYE": 9}
 
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -264,6 +268,8 @@ def load(path: str = LIB_PATH):
     lib.mi_ba_num_params.restype = C.c_int32
     lib.mi_ba_num_params.argtypes = [C.c_int32]
     lib.mi_ba_device_count.argtypes = [_i32p]
+    lib.mi_ba_world_to_image.argtypes = [C.c_int32, _dp, C.c_double, C.c_double, _dp, _dp]
+    lib.mi_ba_image_to_world.argtypes = [C.c_int32, _dp, C.c_double, C.c_double, _dp, _dp]
     lib.mi_ba_default_options.argtypes = [C.POINTER(Options)]
     lib.mi_ba_default_options.restype = None
     lib.mi_ba_setup_stats.argtypes = [C.POINTER(Options), C.POINTER(Problem), C.POINTER(SetupInfo)]
@@ -772,6 +778,24 @@ def device_count() -> int:
     return n.value
 
 
+def world_to_image(model: int, params, u: float, v: float):
+    """Camera::WorldToImage: normalized camera coordinates to pixels (host only)."""
+    prm = np.ascontiguousarray(params, np.float64)
+    x, y = C.c_double(), C.c_double()
+    check(load().mi_ba_world_to_image(int(model), _ptr(prm, _dp), float(u), float(v), C.byref(x), C.byref(y)),
+          "mi_ba_world_to_image")
+    return x.value, y.value
+
+
+def image_to_world(model: int, params, x: float, y: float):
+    """Camera::ImageToWorld: pixels to normalized camera coordinates (host only)."""
+    prm = np.ascontiguousarray(params, np.float64)
+    u, v = C.c_double(), C.c_double()
+    check(load().mi_ba_image_to_world(int(model), _ptr(prm, _dp), float(x), float(y), C.byref(u), C.byref(v)),
+          "mi_ba_image_to_world")
+    return u.value, v.value
+
+
 def setup_stats(options: Options, scene: Scene) -> SetupInfo:
     info = SetupInfo()
     p = scene.problem()
@@ -951,7 +975,11 @@ def convert_cameras(scene: Scene, models) -> Scene:
         m = int(models[c % len(models)])
         ids.append(m)
         params.extend({SIMPLE_PINHOLE: [f, cx, cy], PINHOLE: [f, f * 1.01, cx, cy], SIMPLE_RADIAL: [f, cx, cy, k],
-                       RADIAL: [f, cx, cy, k, -0.01], OPENCV: [f, f * 0.99, cx, cy, k, 0.01, 1e-4, -1e-4]}[m])
+                       RADIAL: [f, cx, cy, k, -0.01], OPENCV: [f, f * 0.99, cx, cy, k, 0.01, 1e-4, -1e-4],
+                       OPENCV_FISHEYE: [f, f * 0.99, cx, cy, k, 0.01, -1e-3, 1e-3],
+                       FOV: [f, f * 1.01, cx, cy, 0.9],
+                       SIMPLE_RADIAL_FISHEYE: [f, cx, cy, k],
+                       RADIAL_FISHEYE: [f, cx, cy, k, -0.01]}[m])
     out = scene.copy()
     out.camera_models = np.array(ids, np.int32)
     out.camera_params = np.array(params, np.float64)
