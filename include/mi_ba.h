@@ -574,6 +574,11 @@ mi_ba_status mi_ba_context_set_host_reducer(mi_ba_context* ctx, int32_t rank, in
  *                           the memory-side cache right before it (semantic contexts):
  *                           1 observations, 2 image ids, 4 point ids, 8 points;
  *                           default 15, 0 off
+ *   "linearize_fusion"      bit mask of the linearization step's small kernels carried by
+ *                           their neighbours' launches (same results bit for bit):
+ *                           1 pair tables + image records + input warm-up in one launch,
+ *                           2 deferred chunk list laid out by the ordering kernel,
+ *                           4 pair blocks in the cost sums' launch; default 1, 0 off
  *   "semantic_flat_coarse"  the flat pass's pixel box from a rotation and a translation
  *                           group of the stencil classes: 2 (default) with the camera
  *                           model's Jacobian at the centre, 1 with |A| bounded from the

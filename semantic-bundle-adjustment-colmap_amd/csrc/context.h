@@ -105,6 +105,7 @@ struct mi_ba_context {
   int warm_unroll = 4;                 // "warm_unroll": loads in flight per lane of the warm-up (4 or 8)
   int warm_wgs = 2048;                 // workgroups of the warm-up kernel (0: one per CU)
   int lin_order = 0;                   // 0 reprojection kernel first, 1 semantic pass first
+  int lin_fusion = 1;                  // "linearize_fusion": 1 step prologue (default), 2 order + compact, 4 step epilogue
   hipStream_t lin_side = nullptr;
   hipEvent_t lin_ev[2] = {nullptr, nullptr};
   int sem_diag = 0;      // "semantic_diag" 1: downloaded status is offset by +0x1000 for samples the flat test

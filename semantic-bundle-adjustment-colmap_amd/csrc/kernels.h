@@ -21,6 +21,11 @@ void launch_reproj_jacobian(const DevProblem& p, double2* r, double* J, double* 
 // mask: bit 0 observations, 1 image ids, 2 point ids, 3 points; wgs <= 0: one workgroup per CU
 void launch_touch_inputs(const DevProblem& p, unsigned* sink, hipStream_t s, int mask = 15, int wgs = 0,
                          int unroll = 4);
+// The warm-up's ranges and workgroup count, for a launch that carries the
+// warm-up as one of its block ranges (the step prologue, semantic.hip).
+struct TouchRanges;  // step_bodies.h
+TouchRanges touch_input_ranges(const DevProblem& p, int mask);
+int touch_workgroups(int wgs);
 int reproj_grid(int64_t nb);
 
 // Cost 0.5*sum(rho) of every reduced block at parameters (qt, cam, X).
@@ -37,6 +42,18 @@ void launch_sum(const double* partial, int64_t n, double* out, hipStream_t s, do
 // workgroups; scratch1: kSumScratch doubles, zeroed tickets).
 void launch_sum2(const double* p1, int64_t n1, double* out1, double* scratch1, const double* p2, int64_t n2,
                  double* out2, hipStream_t s);
+// launch_sum2 and the semantic pair blocks in one launch (the step epilogue):
+// pair_blk[p][0..vals) = the sum of pair p's chunk partials cpart[pair_chunk0[p]
+// + j][0..vals), j < ceil(pair_cnt[p] / 64), in chunk order.
+struct PairBlocks {
+  const uint32_t* pair_cnt;
+  const uint32_t* pair_chunk0;
+  const double* cpart;
+  double* pair_blk;
+  int npairs, vals, blk_stride;
+};
+void launch_sum2_pairs(const double* p1, int64_t n1, double* out1, double* scratch1, const double* p2, int64_t n2,
+                       double* out2, const PairBlocks& pb, hipStream_t s);
 
 // Point side: Jacobi scale (first), LM diagonal (when !reuse_diag) and the
 // damped inverse Vinv[P][6] of V_p + Lambda_p.

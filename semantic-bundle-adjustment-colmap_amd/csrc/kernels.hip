@@ -16,6 +16,7 @@
 #include "ba_math.h"
 #include "device.h"
 #include "kernels.h"
+#include "step_bodies.h"
 
 namespace miba {
 
@@ -634,25 +635,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WPE))) void 
 // zero[0..nzero) is cleared too (the step's scalar slots: one launch fewer
 // than a separate memset ahead of it).
 __global__ void pack_images_kernel(DevProblem p, double* __restrict__ rec, double* __restrict__ zero, int nzero) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < nzero) zero[k] = 0.0;
-  if (k >= p.num_images) return;
-  const uint32_t cam = p.img_cam[k];
-  double* o = rec + kImgRec * (size_t)k;
-#pragma unroll
-  for (int m = 0; m < 7; ++m) o[m] = p.qt[8 * (size_t)k + m];
-  o[7] = __longlong_as_double(
-      (long long)(p.img_flags[k] | ((p.cam_var[cam] != 0 ? 1u : 0u) << 8) | ((uint32_t)p.cam_model[cam] << 16)));
-#pragma unroll
-  for (int m = 0; m < 8; ++m) o[8 + m] = p.cam[8 * (size_t)cam + m];
-  const double q[4] = {o[0], o[1], o[2], o[3]};
-  double R[9];
-  unit_quat_matrix(q, R);
-#pragma unroll
-  for (int m = 0; m < 9; ++m) o[16 + m] = R[m];
-  o[25] = fabs(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] - 1.0) <= 1e-12 ? 1.0 : 0.0;
-#pragma unroll
-  for (int m = 26; m < kImgRec; ++m) o[m] = 0.0;
+  pack_image_record(p, rec, zero, nzero, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 template <int M>
@@ -792,6 +775,31 @@ __global__ __launch_bounds__(256) void sum2_kernel(const double* __restrict__ p1
     group_sum(p2, n2, out2, scratch + kSumGroups + 1,
               reinterpret_cast<unsigned*>(scratch + kSumGroups + 1 + kSumGroups2), kSumGroups2,
               blockIdx.x - kSumGroups, sred, &last);
+}
+
+// The step epilogue ("linearize_fusion" bit 4): sum2_kernel's two sums and
+// the semantic pair blocks (pair_reduce_kernel's body) in one launch, three
+// independent workgroup ranges.  Workgroups past the sums take two pairs
+// each: threads 0..127 the first, 128..255 the second.
+__global__ __launch_bounds__(256) void sum2_pairs_kernel(const double* __restrict__ p1, int64_t n1,
+                                                         double* __restrict__ out1, double* __restrict__ scratch,
+                                                         const double* __restrict__ p2, int64_t n2,
+                                                         double* __restrict__ out2, PairBlocks pb) {
+  __shared__ double sred[4];
+  __shared__ bool last;
+  if (blockIdx.x < kSumGroups) {
+    group_sum(p1, n1, out1, scratch, reinterpret_cast<unsigned*>(scratch + kSumGroups), kSumGroups, blockIdx.x, sred,
+              &last);
+  } else if (blockIdx.x < kSumGroups + kSumGroups2) {
+    group_sum(p2, n2, out2, scratch + kSumGroups + 1,
+              reinterpret_cast<unsigned*>(scratch + kSumGroups + 1 + kSumGroups2), kSumGroups2,
+              blockIdx.x - kSumGroups, sred, &last);
+  } else {
+    const int p = 2 * ((int)blockIdx.x - (kSumGroups + kSumGroups2)) + ((int)threadIdx.x >> 7);
+    if (p < pb.npairs)
+      pair_block_value(pb.pair_cnt, pb.pair_chunk0, pb.cpart, pb.pair_blk, pb.vals, pb.blk_stride, p,
+                       threadIdx.x & 127);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -3540,33 +3548,12 @@ int reproj_grid(int64_t nb) { return (int)grid_for(nb, 64); }
 // (linearize_warm_inputs).  One launch of few workgroups (one per CU): it
 // runs beside the semantic deferred pass and should take as little of the
 // CUs' wave slots as it can.  The sink is written only for an impossible sum.
-struct TouchRanges {
-  const uint4* ptr[5];
-  int64_t n16[5];
-};
-
 template <int U>
 __global__ __launch_bounds__(256) void touch_kernel(TouchRanges t, unsigned* sink) {
-  unsigned acc = 0u;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-#pragma unroll
-  for (int q = 0; q < 5; ++q) {
-    const uint4* a = t.ptr[q];
-    const int64_t n = t.n16[q];
-    int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    for (; k + (U - 1) * stride < n; k += U * stride) {
-      uint4 v[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) v[u] = a[k + u * stride];  // U loads in flight per lane
-#pragma unroll
-      for (int u = 0; u < U; ++u) acc ^= v[u].x ^ v[u].w;
-    }
-    for (; k < n; k += stride) acc ^= a[k].x;
-  }
-  if (acc == 0x9e3779b9u && t.n16[0] < 0) *sink = acc;
+  touch_ranges<U>(t, sink, blockIdx.x, gridDim.x);
 }
 
-void launch_touch_inputs(const DevProblem& p, unsigned* sink, hipStream_t s, int mask, int wgs, int unroll) {
+TouchRanges touch_input_ranges(const DevProblem& p, int mask) {
   // mask bits: 1 observations, 2 image ids, 4 point ids, 8 points; the ids
   // in the layout the kernel reads (packed: both in obs_ids + wave_pt0)
   TouchRanges t{};
@@ -3584,6 +3571,10 @@ void launch_touch_inputs(const DevProblem& p, unsigned* sink, hipStream_t s, int
     t.ptr[q] = reinterpret_cast<const uint4*>(ptrs[q]);
     t.n16[q] = ptrs[q] && (mask & bit[q]) ? bytes[q] / 16 : 0;
   }
+  return t;
+}
+
+int touch_workgroups(int wgs) {
   if (wgs <= 0) {  // one workgroup per CU
     int dev = 0;
     wgs = 256;
@@ -3591,6 +3582,12 @@ void launch_touch_inputs(const DevProblem& p, unsigned* sink, hipStream_t s, int
         wgs <= 0)
       wgs = 256;
   }
+  return wgs;
+}
+
+void launch_touch_inputs(const DevProblem& p, unsigned* sink, hipStream_t s, int mask, int wgs, int unroll) {
+  const TouchRanges t = touch_input_ranges(p, mask);
+  wgs = touch_workgroups(wgs);
   if (unroll >= 8)
     hipLaunchKernelGGL(touch_kernel<8>, dim3(wgs), dim3(256), 0, s, t, sink);
   else
@@ -3808,6 +3805,12 @@ void launch_sum2(const double* p1, int64_t n1, double* out1, double* scratch1, c
                  double* out2, hipStream_t s) {
   hipLaunchKernelGGL(sum2_kernel, dim3(kSumGroups + kSumGroups2), dim3(256), 0, s, p1, n1, out1, scratch1, p2, n2,
                      out2);
+}
+
+void launch_sum2_pairs(const double* p1, int64_t n1, double* out1, double* scratch1, const double* p2, int64_t n2,
+                       double* out2, const PairBlocks& pb, hipStream_t s) {
+  hipLaunchKernelGGL(sum2_pairs_kernel, dim3(kSumGroups + kSumGroups2 + (pb.npairs + 1) / 2), dim3(256), 0, s, p1, n1,
+                     out1, scratch1, p2, n2, out2, pb);
 }
 
 // With scratch the list is always summed by the 64-workgroup pass (the order

@@ -1085,8 +1085,20 @@ mi_ba_status context_linearize(mi_ba_context* ctx, double* cost_out) {
   hipEvent_t stop;
   ctx->jcm_stale = true;
   ctx->xcm_stale = true;
-  // image records + the scalar slots zeroed in one launch
-  launch_pack_images(d, ctx->img_rec.ptr, s, ctx->scalars.ptr, kNumScalars);
+  // linearize_fusion (default 1; 0: ten launches per step): the bookkeeping
+  // kernels carried by their neighbours' launches, in the product layout only
+  // (semantic term, two-pass route, warm-up on, compaction on): 1 the step
+  // prologue below, 2 and 4 in semantic_linearize.  Kernel boundaries stay the
+  // only synchronisation.
+  int fusion = ctx->sem && ctx->lin_warm && d.nb > 0 && ctx->sem_compact && semantic_step_fusable(ctx)
+                   ? ctx->lin_fusion
+                   : 0;
+#ifdef MI_BA_AB_VARIANTS
+  if (ctx->lin_overlap || ctx->lin_order || ctx->lin_warm_conc || ctx->sem_prep_early) fusion = 0;
+#endif
+  // image records + the scalar slots zeroed in one launch (fusion 1: in the
+  // step prologue, with the semantic pair tables and the input warm-up)
+  if (!(fusion & 1)) launch_pack_images(d, ctx->img_rec.ptr, s, ctx->scalars.ptr, kNumScalars);
 #ifdef MI_BA_AB_VARIANTS
   // Step layouts measured slower than the default (tools build only):
   // linearize_overlap: 1 the semantic kernels on a second stream beside the
@@ -1180,8 +1192,14 @@ mi_ba_status context_linearize(mi_ba_context* ctx, double* cost_out) {
   hipEvent_t wstop = nullptr;
   if (ctx->sem && ctx->lin_warm && d.nb > 0) {
     timer_begin(ctx, "input_warm", &wstop);
-    launch_touch_inputs(d, reinterpret_cast<unsigned*>(ctx->scalars.ptr + kNumScalars - 1), s, ctx->lin_warm,
-                        ctx->warm_wgs, ctx->warm_unroll);
+    unsigned* sink = reinterpret_cast<unsigned*>(ctx->scalars.ptr + kNumScalars - 1);
+    if (fusion & 1) {
+      mi_ba_status st = semantic_step_prologue(ctx, s, ctx->scalars.ptr, kNumScalars, sink, ctx->lin_warm,
+                                               ctx->warm_wgs, ctx->warm_unroll);
+      if (st != MI_BA_OK) return st;
+    } else {
+      launch_touch_inputs(d, sink, s, ctx->lin_warm, ctx->warm_wgs, ctx->warm_unroll);
+    }
     timer_end(ctx, wstop);
   }
   timer_begin_after(ctx, "reproj_jacobian", wstop, &stop);  // starts at the warm-up's stop event
@@ -1194,7 +1212,7 @@ mi_ba_status context_linearize(mi_ba_context* ctx, double* cost_out) {
   if (sem_after) {
     mi_ba_status st = semantic_linearize(ctx, ctx->scalars.ptr + kSemCost, false, nullptr, nullptr, stop,
                                          d.nb ? ctx->partial.ptr : nullptr, reproj_grid(d.nb),
-                                         ctx->scalars.ptr + kCost, ctx->sum_ws.ptr, nullptr, prep_ev);
+                                         ctx->scalars.ptr + kCost, ctx->sum_ws.ptr, nullptr, prep_ev, fusion);
     if (st != MI_BA_OK) return st;
   } else if (d.nb) {
     launch_sum(ctx->partial.ptr, reproj_grid(d.nb), ctx->scalars.ptr + kCost, s, ctx->sum_ws.ptr);
@@ -2462,6 +2480,13 @@ mi_ba_status mi_ba_set_tuning(mi_ba_context* ctx, const char* key, int32_t value
   // 1: one wave per 64-sample chunk, 4: one wave per stencil parameter group
   if (std::strcmp(key, "semantic_deferred_waves") == 0 && (value == 1 || value == 4)) {
     ctx->sem_dwaves = value;
+    return MI_BA_OK;
+  }
+  // bit mask: 1 step prologue (pair tables + image records + input warm-up in
+  // one launch), 2 chunk list laid out by the ordering kernel, 4 pair blocks
+  // in the cost sums' launch; 0: the ten separate launches
+  if (std::strcmp(key, "linearize_fusion") == 0 && value >= 0 && value <= 7) {
+    ctx->lin_fusion = value;
     return MI_BA_OK;
   }
   if (std::strcmp(key, "semantic_deferred_compact") == 0 && (value == 0 || value == 1)) {

@@ -92,6 +92,10 @@ struct SemanticState {
   DevArray<uint2> chunks;                  // (pair, first entry): 64-entry chunks of every pair region
   DevArray<uint2> dchunks;                 // the chunks the flat pass filled (deferred_compact_kernel), same regions
   DevArray<uint32_t> dcount;               // [model] their number
+  DevArray<uint32_t> model_pairs;          // each model's pairs in pair order (model-major)
+  DevArray<uint4> pair_ord;                // [npairs] the pair's model list begin, its place in model_pairs,
+                                           // model | last-of-model << 31, model_chunks[model]
+  bool order_compact = false;              // no model has more pairs than deferred_order_kernel<true> takes
   int n_cu = 256;                          // compute units (the deferred pass's resident grid)
   int dwaves_blocks[kNumModels] = {};      // resident four-wave deferred workgroups per CU (occupancy query), per model
   int model_chunks[kNumModels + 1] = {};   // chunk range of each camera model
@@ -120,15 +124,23 @@ void semantic_destroy(mi_ba_context* ctx);
 // a second cost sum (the reprojection partials) launched together with the
 // semantic one.  after_flat (optional): called once the flat pass is
 // enqueued, before the deferred pass (the input warm-up's launch point).
+// fusion: the "linearize_fusion" bits that apply (the step's product layout).
 mi_ba_status semantic_linearize(mi_ba_context* ctx, double* d_cost, bool write_samples,
                                 hipStream_t deferred_stream = nullptr, hipEvent_t flat_done = nullptr,
                                 hipEvent_t timer_start = nullptr, const double* other_partial = nullptr,
                                 int64_t other_n = 0, double* other_out = nullptr, double* other_scratch = nullptr,
                                 const std::function<mi_ba_status()>& after_flat = nullptr,
-                                hipEvent_t prep_done = nullptr);
+                                hipEvent_t prep_done = nullptr, int fusion = 0);
 // The pair tables of one linearization on `stream` (semantic_linearize does
 // it itself unless given prep_done, the event after an earlier call).
 mi_ba_status semantic_pair_prep(mi_ba_context* ctx, hipStream_t stream);
+// The step prologue ("linearize_fusion" bit 1): the pair tables, the image
+// records with the cleared scalar slots zero[0..nzero), and the input warm-up
+// (launch_touch_inputs' arguments) in one launch on `stream`; only where
+// semantic_step_fusable says so.  semantic_linearize is then given fusion bit 1.
+bool semantic_step_fusable(const mi_ba_context* ctx);
+mi_ba_status semantic_step_prologue(mi_ba_context* ctx, hipStream_t stream, double* zero, int nzero, unsigned* sink,
+                                    int warm_mask, int warm_wgs, int warm_unroll);
 // ExportSemanticErrorToCSV rows of the ordered image pair (image1, image2) at
 // the current parameters (mi_ba_semantic_export).
 mi_ba_status semantic_export(mi_ba_context* ctx, int32_t image1, int32_t image2, int64_t* count, int32_t* pixels,

@@ -24,6 +24,7 @@
 #include "ba_math.h"
 #include "kernels.h"
 #include "semantic.h"
+#include "step_bodies.h"
 
 namespace miba {
 
@@ -449,21 +450,21 @@ __device__ inline void stencil_prep(const double* q1, const double* t1, const do
   }
 }
 
-// Two pairs per 64-lane workgroup: lanes 0..27 of each half fill the stencil
-// tables, lane 28 the pair's base constants.  The pair's accumulator record
-// (blk_stride doubles of pair_blk) and deferred-sample count are cleared here
-// too (two launches fewer than separate memsets).
-__global__ void semantic_pair_prep_kernel(const SemPair* __restrict__ pairs, int npairs, const double* __restrict__ qt,
-                                          const double* __restrict__ cam, const uint32_t* __restrict__ img_cam,
-                                          const uint32_t* __restrict__ img_flags,
-                                          const uint32_t* __restrict__ raster_slot,
-                                          const SlotInfo* __restrict__ slots, double rel_step,
-                                          PairConst* __restrict__ out, double* __restrict__ pair_blk, int blk_stride,
-                                          uint32_t* __restrict__ pair_cnt, uint32_t* __restrict__ zero_n = nullptr,
-                                          int nzero = 0) {
-  const int k = blockIdx.x * 2 + (threadIdx.x >> 5);
-  const int lane = threadIdx.x & 31;
-  if (zero_n && blockIdx.x == 0 && (int)threadIdx.x < nzero) zero_n[threadIdx.x] = 0u;  // the deferred pass's counts
+// Per-pair record: loss-corrected J'J (packed 12x12 upper, 78) and J'r (12).
+constexpr int kPairVals = 78 + 12;
+constexpr int kPairStride = 96;  // padded record per pair
+constexpr int kSemRow = 13;      // LDS row: corrected J (12), corrected r
+
+// One pair's tables by 32 lanes: lanes 0..27 fill the stencil tables, lane 28
+// the pair's base constants.  The pair's accumulator record (blk_stride
+// doubles of pair_blk) and deferred-sample count are cleared here too (two
+// launches fewer than separate memsets).
+__device__ inline void pair_prep_body(int k, int lane, const SemPair* __restrict__ pairs, int npairs,
+                                      const double* __restrict__ qt, const double* __restrict__ cam,
+                                      const uint32_t* __restrict__ img_cam, const uint32_t* __restrict__ img_flags,
+                                      const uint32_t* __restrict__ raster_slot, const SlotInfo* __restrict__ slots,
+                                      double rel_step, PairConst* __restrict__ out, double* __restrict__ pair_blk,
+                                      int blk_stride, uint32_t* __restrict__ pair_cnt) {
   if (k >= npairs) return;
   for (int e = lane; e < blk_stride; e += 32) pair_blk[(size_t)k * blk_stride + e] = 0.0;
   if (pair_cnt && lane == 31) pair_cnt[k] = 0u;
@@ -519,10 +520,62 @@ __global__ void semantic_pair_prep_kernel(const SemPair* __restrict__ pairs, int
   stencil_bounds(P.q2, P.t2, rel_step, &P.rho2, P.dt2);
 }
 
-// Per-pair record: loss-corrected J'J (packed 12x12 upper, 78) and J'r (12).
-constexpr int kPairVals = 78 + 12;
-constexpr int kPairStride = 96;  // padded record per pair
-constexpr int kSemRow = 13;      // LDS row: corrected J (12), corrected r
+// Two pairs per 64-lane workgroup; workgroup 0 also clears the deferred
+// pass's per-model counts zero_n[0..nzero).
+__global__ void semantic_pair_prep_kernel(const SemPair* __restrict__ pairs, int npairs, const double* __restrict__ qt,
+                                          const double* __restrict__ cam, const uint32_t* __restrict__ img_cam,
+                                          const uint32_t* __restrict__ img_flags,
+                                          const uint32_t* __restrict__ raster_slot,
+                                          const SlotInfo* __restrict__ slots, double rel_step,
+                                          PairConst* __restrict__ out, double* __restrict__ pair_blk, int blk_stride,
+                                          uint32_t* __restrict__ pair_cnt, uint32_t* __restrict__ zero_n = nullptr,
+                                          int nzero = 0) {
+  if (zero_n && blockIdx.x == 0 && (int)threadIdx.x < nzero) zero_n[threadIdx.x] = 0u;  // the deferred pass's counts
+  pair_prep_body(blockIdx.x * 2 + (threadIdx.x >> 5), threadIdx.x & 31, pairs, npairs, qt, cam, img_cam, img_flags,
+                 raster_slot, slots, rel_step, out, pair_blk, blk_stride, pair_cnt);
+}
+
+// The step prologue ("linearize_fusion" bit 1): one launch of three
+// independent workgroup ranges.  Workgroups [0, nprep): the pair tables,
+// eight pairs each (lowest indices: dispatched first, the flat pass's inputs);
+// [nprep, nprep + npack): the image records and the cleared scalar slots
+// (pack_images_kernel's body); the other nwarm: the input warm-up
+// (touch_kernel's body, striding by nwarm).  No range reads what another
+// writes: the records are read by the reprojection kernel, the tables by the
+// flat pass, both behind the kernel boundary.
+struct PrepArgs {
+  const SemPair* pairs;
+  int npairs;
+  const double* qt;
+  const double* cam;
+  const uint32_t* img_cam;
+  const uint32_t* img_flags;
+  const uint32_t* raster_slot;
+  const SlotInfo* slots;
+  double rel_step;
+  PairConst* out;
+  double* pair_blk;
+  uint32_t* pair_cnt;
+  uint32_t* dcount;
+};
+
+template <int U>
+__global__ __launch_bounds__(256) void step_prologue_kernel(PrepArgs a, int nprep, DevProblem p,
+                                                            double* __restrict__ rec, double* __restrict__ zero,
+                                                            int nzero, int npack, TouchRanges t, unsigned* sink,
+                                                            int nwarm) {
+  const int b = blockIdx.x;
+  if (b < nprep) {
+    if (b == 0 && (int)threadIdx.x < kNumModels) a.dcount[threadIdx.x] = 0u;  // the deferred pass's counts
+    pair_prep_body(b * 8 + (threadIdx.x >> 5), threadIdx.x & 31, a.pairs, a.npairs, a.qt, a.cam, a.img_cam,
+                   a.img_flags, a.raster_slot, a.slots, a.rel_step, a.out, a.pair_blk, kPairStride, a.pair_cnt);
+  } else if (b < nprep + npack) {
+    pack_image_record(p, rec, zero, nzero, (b - nprep) * 256 + (int)threadIdx.x);
+  } else {
+    touch_ranges<U>(t, sink, b - nprep - npack, nwarm);
+  }
+}
+
 
 // One workgroup per pair-aligned tile of <= 256 samples, one lane per sample:
 // centre residual (reference sequence), the CENTRAL stencil over the
@@ -1517,7 +1570,8 @@ __global__ __launch_bounds__(kBlock) void semantic_flat_kernel(SemArgs ak, const
                                                                double* __restrict__ cost_partial,
                                                                double* __restrict__ r_out,
                                                                int32_t* __restrict__ status_out,
-                                                               double* __restrict__ J_out, int write_samples) {
+                                                               double* __restrict__ J_out, int write_samples,
+                                                               uint32_t* __restrict__ pair_cnt) {
   __shared__ double sred[kBlock / 64];
   __shared__ float spal[LP ? 256 : 1];
   const SemTile t = tiles[blockIdx.x];
@@ -1652,6 +1706,10 @@ __global__ __launch_bounds__(kBlock) void semantic_flat_kernel(SemArgs ak, const
   // tile): deferred_order_kernel lists them per pair in sample order
   const unsigned long long bal = __ballot(deferred);
   if (lane == 0) dmask[(size_t)blockIdx.x * (kBlock / 64) + (tid >> 6)] = bal;
+  // pair_cnt ("linearize_fusion" bit 2; zeroed by the pair prep): the pair's
+  // deferred samples counted here, integer adds read behind the kernel
+  // boundary (deferred_order_kernel<true> lays out the chunk list from them)
+  if (pair_cnt && lane == 0 && bal) atomicAdd(pair_cnt + t.pair, (uint32_t)__popcll(bal));
   double v = cost;
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   if (lane == 0) sred[tid >> 6] = v;
@@ -1978,16 +2036,40 @@ __global__ __launch_bounds__(256) void semantic_deferred_waves_kernel(SemArgs ak
 // popcounts, a workgroup scan, each set bit's offset.  pair_cnt = their
 // number.  Sample order makes every chunk of the deferred pass, hence every
 // pair block sum, the same run to run.
+//
+// COMPACT ("linearize_fusion" bit 2): the deferred pass's chunk list in the
+// same launch.  pair_cnt then holds the flat pass's counts already (read only
+// here); the pair's live chunks (p, 64 c) go behind those of the pairs that
+// precede it in its model's pair list (mlist, pair order; ord[p] = the list's
+// begin, p's position, model | last-of-model << 31, the model's chunk region):
+// every workgroup sums ceil(pair_cnt[q] / 64) over those pairs itself, so no
+// workgroup waits for another and the list is pair-major, the same run to
+// run.  The model's last pair writes the list's length dcount[model].
+template <bool COMPACT>
 __global__ __launch_bounds__(256) void deferred_order_kernel(const unsigned long long* __restrict__ dmask,
                                                              const uint32_t* __restrict__ pair_tile0,
                                                              const SemPair* __restrict__ pairs,
                                                              uint32_t* __restrict__ pair_cnt,
-                                                             uint32_t* __restrict__ dlist) {
+                                                             uint32_t* __restrict__ dlist,
+                                                             const uint4* __restrict__ ord = nullptr,
+                                                             const uint32_t* __restrict__ mlist = nullptr,
+                                                             uint2* __restrict__ dchunks = nullptr,
+                                                             uint32_t* __restrict__ dcount = nullptr) {
   __shared__ uint32_t sc[256];
+  __shared__ uint32_t spre[4];
   const int p = blockIdx.x, tid = threadIdx.x;
   const SemPair pr = pairs[p];
   const uint32_t words = (pr.count + 63) / 64;
   const unsigned long long* mk = dmask + (size_t)pair_tile0[p] * (kBlock / 64);
+  uint4 od = make_uint4(0u, 0u, 0u, 0u);
+  if constexpr (COMPACT) {
+    // chunks of the pairs ahead in the model's list (loads independent of the masks')
+    od = ord[p];
+    uint32_t pre = 0;
+    for (uint32_t q = od.x + tid; q < od.y; q += 256) pre += (pair_cnt[mlist[q]] + 63) / 64;
+    for (int off = 32; off > 0; off >>= 1) pre += __shfl_xor(pre, off, 64);
+    if ((tid & 63) == 0) spre[tid >> 6] = pre;
+  }
   uint32_t base = 0;
   for (uint32_t w0 = 0; w0 < words; w0 += 256) {
     const uint32_t w = w0 + tid;
@@ -2006,7 +2088,16 @@ __global__ __launch_bounds__(256) void deferred_order_kernel(const unsigned long
     base += sc[255];
     __syncthreads();
   }
-  if (tid == 0) pair_cnt[p] = base;
+  if constexpr (COMPACT) {
+    __syncthreads();  // spre (a pair without samples runs no scan round)
+    const uint32_t pre = ((spre[0] + spre[1]) + spre[2]) + spre[3];
+    const uint32_t nch = (base + 63) / 64;  // base = pair_cnt[p], the flat pass's count
+    uint2* out = dchunks + od.w + pre;
+    for (uint32_t c = tid; c < nch; c += 256) out[c] = make_uint2((uint32_t)p, 64 * c);
+    if (tid == 0 && (od.z >> 31)) dcount[od.z & 0x7fffffffu] = pre + nch;
+  } else {
+    if (tid == 0) pair_cnt[p] = base;
+  }
 }
 
 // Pair blocks from the deferred pass's chunk partials, summed in chunk order
@@ -2016,13 +2107,7 @@ __global__ __launch_bounds__(128) void pair_reduce_kernel(const uint32_t* __rest
                                                           const uint32_t* __restrict__ pair_chunk0,
                                                           const double* __restrict__ cpart,
                                                           double* __restrict__ pair_blk) {
-  const int p = blockIdx.x, e = threadIdx.x;
-  if (e >= kPairVals) return;
-  const uint32_t nch = (pair_cnt[p] + 63) / 64;
-  const double* c = cpart + (size_t)pair_chunk0[p] * kPairVals + e;
-  double v = 0.0;
-  for (uint32_t j = 0; j < nch; ++j) v += c[(size_t)j * kPairVals];
-  pair_blk[(size_t)p * kPairStride + e] = v;
+  pair_block_value(pair_cnt, pair_chunk0, cpart, pair_blk, kPairVals, kPairStride, blockIdx.x, threadIdx.x);
 }
 
 // The deferred pass's work list: the static list of every pair's possible
@@ -2036,6 +2121,10 @@ __global__ __launch_bounds__(128) void pair_reduce_kernel(const uint32_t* __rest
 struct ModelRanges {
   int b[kNumModels + 1];
 };
+
+// deferred_order_kernel<true>: most pairs of one model (each workgroup reads
+// the counts of the pairs ahead of its own: 33 MB of L2 reads in all at the cap)
+constexpr int kOrderCompactMaxPairs = 4096;
 
 __global__ __launch_bounds__(256) void deferred_compact_kernel(const uint2* __restrict__ chunks, int nchunks,
                                                                const uint32_t* __restrict__ pair_cnt, ModelRanges mr,
@@ -2545,6 +2634,31 @@ mi_ba_status semantic_create(mi_ba_context* ctx, const mi_ba_semantic* sem) {
       S->model_chunks[m + 1] = (int)chunks.size();
     }
   }
+  // each model's pairs in pair order and each pair's place among them
+  // (deferred_order_kernel<true>); above kOrderCompactMaxPairs pairs of one
+  // model the per-workgroup prefix over them is not worth it and the ordering
+  // and compaction kernels stay apart
+  {
+    std::vector<std::vector<uint32_t>> per(kNumModels);
+    for (int k = 0; k < S->npairs; ++k) per[hs.cam_model[p->image_camera[S->pairs_host[k].j]]].push_back((uint32_t)k);
+    std::vector<uint32_t> mlist;
+    std::vector<uint4> ord(std::max(1, S->npairs), make_uint4(0u, 0u, 0u, 0u));
+    S->order_compact = S->npairs > 0;
+    for (int m = 0; m < kNumModels; ++m) {
+      const uint32_t begin = (uint32_t)mlist.size();
+      if (per[m].size() > (size_t)kOrderCompactMaxPairs) S->order_compact = false;
+      for (size_t r = 0; r < per[m].size(); ++r) {
+        const uint32_t last = r + 1 == per[m].size() ? 0x80000000u : 0u;
+        ord[per[m][r]] = make_uint4(begin, begin + (uint32_t)r, (uint32_t)m | last, (uint32_t)S->model_chunks[m]);
+      }
+      mlist.insert(mlist.end(), per[m].begin(), per[m].end());
+    }
+    if (S->pair_ord.alloc(ord.size()) || S->model_pairs.alloc(std::max<size_t>(1, mlist.size())))
+      return MI_BA_ERR_OUT_OF_MEMORY;
+    if (hipMemcpy(S->pair_ord.ptr, ord.data(), ord.size() * sizeof(uint4), hipMemcpyHostToDevice) ||
+        (!mlist.empty() && hipMemcpy(S->model_pairs.ptr, mlist.data(), mlist.size() * 4, hipMemcpyHostToDevice)))
+      return MI_BA_ERR_HIP;
+  }
   if (S->pair_cnt.alloc(std::max(1, S->npairs)) || S->dlist.alloc(std::max<int64_t>(1, S->ns)) ||
       S->chunks.alloc(std::max<size_t>(1, chunks.size())) || S->dchunks.alloc(std::max<size_t>(1, chunks.size())) ||
       S->dcount.alloc(kNumModels))
@@ -2806,13 +2920,44 @@ mi_ba_status semantic_pair_prep(mi_ba_context* ctx, hipStream_t stream) {
   return hipGetLastError() == hipSuccess ? MI_BA_OK : MI_BA_ERR_HIP;
 }
 
+// The step prologue on `stream`: semantic_pair_prep, launch_pack_images (with
+// the zero[0..nzero) fill) and launch_touch_inputs in one launch.
+mi_ba_status semantic_step_prologue(mi_ba_context* ctx, hipStream_t stream, double* zero, int nzero, unsigned* sink,
+                                    int warm_mask, int warm_wgs, int warm_unroll) {
+  SemanticState* S = ctx->sem;
+  if (!S || S->ns == 0 || S->npairs == 0 || ctx->sem_variant != 6) return MI_BA_ERR_STATE;
+  const DevProblem& d = ctx->dev;
+  SemArgs a = make_args(ctx, d.qt, d.cam);
+  PrepArgs pa{S->pairs.ptr, S->npairs, a.qt, a.cam, a.img_cam, a.img_flags, a.raster_slot, a.slots, a.rel_step,
+              reinterpret_cast<PairConst*>(S->pconst.ptr), S->pair_blk.ptr, S->pair_cnt.ptr, S->dcount.ptr};
+  const int nprep = (S->npairs + 7) / 8;
+  const int npack = (int)((std::max<int64_t>(d.num_images, nzero) + 255) / 256);
+  const int nwarm = touch_workgroups(warm_wgs);
+  const TouchRanges t = touch_input_ranges(d, warm_mask);
+  const dim3 grid((unsigned)(nprep + npack + nwarm));
+  if (warm_unroll >= 8)
+    hipLaunchKernelGGL(step_prologue_kernel<8>, grid, dim3(256), 0, stream, pa, nprep, d, ctx->img_rec.ptr, zero, nzero,
+                       npack, t, sink, nwarm);
+  else
+    hipLaunchKernelGGL(step_prologue_kernel<4>, grid, dim3(256), 0, stream, pa, nprep, d, ctx->img_rec.ptr, zero, nzero,
+                       npack, t, sink, nwarm);
+  return hipGetLastError() == hipSuccess ? MI_BA_OK : MI_BA_ERR_HIP;
+}
+
+// Whether semantic_step_prologue applies to this context's semantic term.
+bool semantic_step_fusable(const mi_ba_context* ctx) {
+  const SemanticState* S = ctx->sem;
+  return S && S->ns > 0 && S->npairs > 0 && ctx->sem_variant == 6;
+}
+
 // deferred_stream: when given (two-pass route), the deferred-sample pass is
 // launched there instead (after an event on ctx->stream marks the flat pass
 // done), and the caller joins it; the cost is complete on ctx->stream.
 mi_ba_status semantic_linearize(mi_ba_context* ctx, double* d_cost, bool write_samples, hipStream_t deferred_stream,
                                 hipEvent_t flat_done, hipEvent_t timer_start, const double* other_partial,
                                 int64_t other_n, double* other_out, double* other_scratch,
-                                const std::function<mi_ba_status()>& after_flat, hipEvent_t prep_done) {
+                                const std::function<mi_ba_status()>& after_flat, hipEvent_t prep_done,
+                                int fusion) {
   SemanticState* S = ctx->sem;
   hipStream_t s = ctx->stream;
   S->samples_valid = write_samples;
@@ -2825,7 +2970,16 @@ mi_ba_status semantic_linearize(mi_ba_context* ctx, double* d_cost, bool write_s
   PairConst* pcs = reinterpret_cast<PairConst*>(S->pconst.ptr);
   hipEvent_t stop;
   timer_begin_after(ctx, "semantic_jacobian", timer_start, &stop);
-  if (prep_done) {
+  // fusion ("linearize_fusion", the step's product layout only): 1 the pair
+  // tables are ready (the step prologue formed them), 2 the flat pass counts
+  // each pair's deferred samples and the ordering kernel lays out the chunk
+  // list, 4 the pair blocks in the cost sums' launch
+  const bool order_compact = (fusion & 2) && ctx->sem_variant == 6 && ctx->sem_compact != 0 && S->order_compact &&
+                             S->model_chunks[kNumModels] > 0 && !deferred_stream;
+  const bool epilogue = (fusion & 4) && ctx->sem_variant == 6 && other_partial && !deferred_stream;
+  if (fusion & 1) {
+    // the step prologue formed the pair tables (semantic_step_prologue)
+  } else if (prep_done) {
     // the pair tables were formed on a side stream beside the reprojection
     // kernel (semantic_pair_prep)
     if (hipStreamWaitEvent(s, prep_done, 0) != hipSuccess) return MI_BA_ERR_HIP;
@@ -2838,12 +2992,17 @@ mi_ba_status semantic_linearize(mi_ba_context* ctx, double* d_cost, bool write_s
     const int ws = write_samples ? 1 | (ctx->sem_diag ? 2 : 0) | (ctx->sem_diag == 2 ? 4 : 0) : 0;
     auto deferred = [&](hipStream_t ds) -> mi_ba_status {
       // each pair's deferred samples in sample order (pair_cnt, dlist)
-      hipLaunchKernelGGL(deferred_order_kernel, dim3(S->npairs), dim3(256), 0, ds, S->dmask.ptr, S->pair_tile0.ptr,
-                         S->pairs.ptr, S->pair_cnt.ptr, S->dlist.ptr);
+      if (order_compact)
+        hipLaunchKernelGGL(deferred_order_kernel<true>, dim3(S->npairs), dim3(256), 0, ds, S->dmask.ptr,
+                           S->pair_tile0.ptr, S->pairs.ptr, S->pair_cnt.ptr, S->dlist.ptr, S->pair_ord.ptr,
+                           S->model_pairs.ptr, S->dchunks.ptr, S->dcount.ptr);
+      else
+        hipLaunchKernelGGL(deferred_order_kernel<false>, dim3(S->npairs), dim3(256), 0, ds, S->dmask.ptr,
+                           S->pair_tile0.ptr, S->pairs.ptr, S->pair_cnt.ptr, S->dlist.ptr);
       // the non-empty chunks, then a resident grid per model looping over them
       const int nall = S->model_chunks[kNumModels];
       const bool compact = ctx->sem_compact != 0;
-      if (nall > 0 && compact) {
+      if (nall > 0 && compact && !order_compact) {
         ModelRanges mr;
         for (int m = 0; m <= kNumModels; ++m) mr.b[m] = S->model_chunks[m];
         // dcount was zeroed by the pair prep kernel (ordered before the flat pass)
@@ -2911,9 +3070,11 @@ mi_ba_status semantic_linearize(mi_ba_context* ctx, double* d_cost, bool write_s
                                S->status.ptr);
         });
       }
-      // pair blocks from the chunk partials, in chunk order
-      hipLaunchKernelGGL(pair_reduce_kernel, dim3(S->npairs), dim3(128), 0, ds, S->pair_cnt.ptr, S->pair_chunk0.ptr,
-                         S->cpart.ptr, S->pair_blk.ptr);
+      // pair blocks from the chunk partials, in chunk order (epilogue: in the
+      // cost sums' launch below)
+      if (!epilogue)
+        hipLaunchKernelGGL(pair_reduce_kernel, dim3(S->npairs), dim3(128), 0, ds, S->pair_cnt.ptr, S->pair_chunk0.ptr,
+                           S->cpart.ptr, S->pair_blk.ptr);
       return MI_BA_OK;
     };
     for (int model = 0; model < kNumModels; ++model) {
@@ -2926,7 +3087,7 @@ mi_ba_status semantic_linearize(mi_ba_context* ctx, double* d_cost, bool write_s
                                                    decltype(coarse_)::value>),
                              dim3(nt), dim3(kBlock), 0, s, a, S->tiles.ptr + t0, pcs,
                              S->dmask.ptr + (size_t)t0 * (kBlock / 64), S->partial.ptr + t0, S->r.ptr, S->status.ptr,
-                             S->J.ptr, ws);
+                             S->J.ptr, ws, order_compact ? S->pair_cnt.ptr : nullptr);
         };
         using T = std::true_type;
         using F = std::false_type;
@@ -2985,6 +3146,15 @@ mi_ba_status semantic_linearize(mi_ba_context* ctx, double* d_cost, bool write_s
     });
   }
 #endif
+  if (epilogue) {
+    // the timer still ends behind the finished pair blocks (it now holds the cost sums too)
+    launch_sum2_pairs(other_partial, other_n, other_out, other_scratch, S->partial.ptr, S->ntiles, d_cost,
+                      PairBlocks{S->pair_cnt.ptr, S->pair_chunk0.ptr, S->cpart.ptr, S->pair_blk.ptr, S->npairs, kPairVals,
+                                 kPairStride},
+                      s);
+    timer_end(ctx, stop);
+    return hipGetLastError() == hipSuccess ? MI_BA_OK : MI_BA_ERR_HIP;
+  }
   timer_end(ctx, stop);
   if (other_partial)
     launch_sum2(other_partial, other_n, other_out, other_scratch, S->partial.ptr, S->ntiles, d_cost, s);
