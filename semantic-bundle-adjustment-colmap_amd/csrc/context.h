@@ -118,6 +118,12 @@ struct mi_ba_context {
   bool sem_dgrid_set = false;
   int sem_dwaves = 4;    // "semantic_deferred_waves": 1 one wave per chunk (semantic_deferred_kernel),
                          // 4 one wave per stencil parameter group (semantic_deferred_waves_kernel)
+  int sem_dpipe = 0;     // "semantic_deferred_pipeline": 1 the four-wave kernel's resident loop loads a chunk's
+                         // record, entries and samples one to three chunks ahead (chunk records carry the
+                         // pair's count and start), 0 every chunk loads its own before it computes (default:
+                         // 1 measured no gain, profiles/dp_ab_deferred_pipeline.jsonl)
+  int sem_dgroups = 0;   // "semantic_deferred_groups": the deferred pass's resident grid in workgroups
+                         // (0: per CU, sem_dgrid / the occupancy query)
   int sem_dvar = 0;      // "semantic_deferred_variant" (tools build): stencil batch / occupancy variants
   int sem_compact = 1;   // "semantic_deferred_compact": the deferred pass over the filled chunks only (resident grid)
   int sem_coarse = 2;    // "semantic_flat_coarse": the flat pass's box from a rotation and a translation group

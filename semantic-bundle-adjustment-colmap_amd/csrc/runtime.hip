@@ -2477,6 +2477,17 @@ mi_ba_status mi_ba_set_tuning(mi_ba_context* ctx, const char* key, int32_t value
     ctx->sem_dgrid_set = true;
     return MI_BA_OK;
   }
+  // 1: the four-wave kernel's chunk loop reads ahead (chunk record, dlist
+  // entries and samples of the chunks to come), 0: each chunk reads its own
+  if (std::strcmp(key, "semantic_deferred_pipeline") == 0 && (value == 0 || value == 1)) {
+    ctx->sem_dpipe = value;
+    return MI_BA_OK;
+  }
+  // the deferred pass's resident grid in workgroups (0: sized per CU)
+  if (std::strcmp(key, "semantic_deferred_groups") == 0 && value >= 0 && value <= (1 << 20)) {
+    ctx->sem_dgroups = value;
+    return MI_BA_OK;
+  }
   // 1: one wave per 64-sample chunk, 4: one wave per stencil parameter group
   if (std::strcmp(key, "semantic_deferred_waves") == 0 && (value == 1 || value == 4)) {
     ctx->sem_dwaves = value;

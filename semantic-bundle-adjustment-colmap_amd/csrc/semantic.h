@@ -91,13 +91,15 @@ struct SemanticState {
   DevArray<uint32_t> dlist;                // [ns] deferred samples (offset in pair), pair regions
   DevArray<uint2> chunks;                  // (pair, first entry): 64-entry chunks of every pair region
   DevArray<uint2> dchunks;                 // the chunks the flat pass filled (deferred_compact_kernel), same regions
+  DevArray<uint2> dext;                    // (pair's count, pair's start) of each dchunks entry ("semantic_deferred_pipeline")
   DevArray<uint32_t> dcount;               // [model] their number
   DevArray<uint32_t> model_pairs;          // each model's pairs in pair order (model-major)
   DevArray<uint4> pair_ord;                // [npairs] the pair's model list begin, its place in model_pairs,
                                            // model | last-of-model << 31, model_chunks[model]
   bool order_compact = false;              // no model has more pairs than deferred_order_kernel<true> takes
   int n_cu = 256;                          // compute units (the deferred pass's resident grid)
-  int dwaves_blocks[kNumModels] = {};      // resident four-wave deferred workgroups per CU (occupancy query), per model
+  int dwaves_blocks[2][kNumModels] = {};   // resident four-wave deferred workgroups per CU (occupancy query), per
+                                           // model; [1]: the pipelined loop
   int model_chunks[kNumModels + 1] = {};   // chunk range of each camera model
   // deterministic sums: the flat pass's deferral masks ([tile][4] words),
   // each pair's first tile and first static chunk, the deferred pass's chunk

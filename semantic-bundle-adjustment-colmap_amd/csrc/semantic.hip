@@ -427,8 +427,9 @@ __device__ inline void stencil_prep(const double* q1, const double* t1, const do
   }
   if (grp == 1 || grp == 3) return;
   const double* q = grp == 0 ? q1 : q2;
-  double qq[4] = {q[0], q[1], q[2], q[3]};
-  qq[k] = pert;
+  double qq[4];  // selects, not an indexed store: the array stays in registers
+#pragma unroll
+  for (int c = 0; c < 4; ++c) qq[c] = c == k ? pert : q[c];
   double Q[9];
   quat_matrix_un(qq, Q);
   const double in = 1.0 / (qq[0] * qq[0] + qq[1] * qq[1] + qq[2] * qq[2] + qq[3] * qq[3]);
@@ -446,7 +447,13 @@ __device__ inline void stencil_prep(const double* q1, const double* t1, const do
   if (minus) {
     double PJ[12];
     quat_plus_jacobian(q, PJ);
-    for (int c = 0; c < 3; ++c) P->pj[(grp == 0 ? 0 : 4) + k][c] = PJ[3 * k + c];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      double v = PJ[c];
+#pragma unroll
+      for (int kk = 1; kk < 4; ++kk) v = kk == k ? PJ[3 * kk + c] : v;
+      P->pj[(grp == 0 ? 0 : 4) + k][c] = v;
+    }
   }
 }
 
@@ -455,11 +462,13 @@ constexpr int kPairVals = 78 + 12;
 constexpr int kPairStride = 96;  // padded record per pair
 constexpr int kSemRow = 13;      // LDS row: corrected J (12), corrected r
 
-// One pair's tables by 32 lanes: lanes 0..27 fill the stencil tables, lane 28
-// the pair's base constants.  The pair's accumulator record (blk_stride
+// One pair's tables by 32 lanes: lanes 0..27 fill the stencil tables, lanes
+// 28..30 the pair's base constants.  The pair's accumulator record (blk_stride
 // doubles of pair_blk) and deferred-sample count are cleared here too (two
-// launches fewer than separate memsets).
-__device__ inline void pair_prep_body(int k, int lane, const SemPair* __restrict__ pairs, int npairs,
+// launches fewer than separate memsets).  Inlined into both kernels: as a
+// called function it cost the step prologue's warm-up range 120 VGPRs and
+// 272 B of scratch, half the residency of touch_kernel.
+__device__ __forceinline__ void pair_prep_body(int k, int lane, const SemPair* __restrict__ pairs, int npairs,
                                       const double* __restrict__ qt, const double* __restrict__ cam,
                                       const uint32_t* __restrict__ img_cam, const uint32_t* __restrict__ img_flags,
                                       const uint32_t* __restrict__ raster_slot, const SlotInfo* __restrict__ slots,
@@ -468,56 +477,75 @@ __device__ inline void pair_prep_body(int k, int lane, const SemPair* __restrict
   if (k >= npairs) return;
   for (int e = lane; e < blk_stride; e += 32) pair_blk[(size_t)k * blk_stride + e] = 0.0;
   if (pair_cnt && lane == 31) pair_cnt[k] = 0u;
-  if (lane > 28) return;
+  if (lane > 30) return;
   const SemPair pr = pairs[k];
-  if (lane < 28) {
-    const double* a1 = qt + 8 * (size_t)pr.i;
-    const double* a2 = qt + 8 * (size_t)pr.j;
-    const double q1[4] = {a1[0], a1[1], a1[2], a1[3]}, t1[3] = {a1[4], a1[5], a1[6]};
-    const double q2[4] = {a2[0], a2[1], a2[2], a2[3]}, t2[3] = {a2[4], a2[5], a2[6]};
-    stencil_prep(q1, t1, q2, t2, rel_step, lane, out + k);
-    return;
-  }
-  PairConst& P = out[k];
   const double* a1 = qt + 8 * (size_t)pr.i;
   const double* a2 = qt + 8 * (size_t)pr.j;
-  for (int m = 0; m < 4; ++m) { P.q1[m] = a1[m]; P.q2[m] = a2[m]; }
-  for (int m = 0; m < 3; ++m) { P.t1[m] = a1[4 + m]; P.t2[m] = a2[4 + m]; }
-  // PoseInverse + QuaternionToRotation (pose1_stage), t_inv (pose1_world)
-  Pose1Stage s;
-  const double zero[3] = {0.0, 0.0, 0.0};
-  pose1_stage(P.q1, zero, s);
-  {
-    const double* q1 = P.q1;
-    const double sc = 1.0 / sqrt(q1[0] * q1[0] + q1[1] * q1[1] + q1[2] * q1[2] + q1[3] * q1[3]);
-    const double qi[4] = {sc * q1[0], -(sc * q1[1]), -(sc * q1[2]), -(sc * q1[3])};
-    // quat_rotate_point(qi, .) normalisation
-    const double scale = 1.0 / sqrt(qi[0] * qi[0] + qi[1] * qi[1] + qi[2] * qi[2] + qi[3] * qi[3]);
-    for (int m = 0; m < 4; ++m) P.uqi[m] = scale * qi[m];
+  if (lane < 28) {
+    // the poses read where they lie: the lane's own coordinate is an indexed
+    // load from memory, not from a register array
+    stencil_prep(a1, a1 + 4, a2, a2 + 4, rel_step, lane, out + k);
+    return;
   }
-  P.ti[0] = -(s.R[0] * P.t1[0] + s.R[1] * P.t1[1] + s.R[2] * P.t1[2]);
-  P.ti[1] = -(s.R[3] * P.t1[0] + s.R[4] * P.t1[1] + s.R[5] * P.t1[2]);
-  P.ti[2] = -(s.R[6] * P.t1[0] + s.R[7] * P.t1[1] + s.R[8] * P.t1[2]);
-  unit_quat(P.q2, P.u2);
-  unit_quat_matrix(P.u2, P.R2);
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c)
-      P.C[3 * r + c] = P.R2[3 * r] * s.R[c] + P.R2[3 * r + 1] * s.R[3 + c] + P.R2[3 * r + 2] * s.R[6 + c];
-  const double* K = cam + 8 * (size_t)img_cam[pr.j];
-  for (int m = 0; m < 8; ++m) P.K2[m] = K[m];
-  P.var1 = pr.var1;
-  P.var2 = pr.var2;
-  P.mask1 = (img_flags[pr.i] >> 1) & 7u;
-  P.mask2 = (img_flags[pr.j] >> 1) & 7u;
-  P.slot = raster_slot[pr.j];
-  const SlotInfo si = slots[P.slot];
-  P.H2 = (uint32_t)si.H;
-  P.W2 = (uint32_t)si.W;
-  P.TW2 = (uint32_t)si.TW;
-  P.roff = si.off;
-  P.toff = si.toff;
-  stencil_bounds(P.q1, P.t1, rel_step, &P.rho1, P.dt1);
-  stencil_bounds(P.q2, P.t2, rel_step, &P.rho2, P.dt2);
+  // The base constants by three lanes, each value by the operation sequence
+  // it always had: lane 28 pose 1's, lane 29 pose 2's and the raster's, lane
+  // 30 the product C (it forms both rotations again).  One lane forming all of
+  // them held some 120 VGPRs; each share stays below 64.
+  PairConst& P = out[k];
+  const double zero[3] = {0.0, 0.0, 0.0};
+  if (lane == 28) {
+    const double q1[4] = {a1[0], a1[1], a1[2], a1[3]}, t1[3] = {a1[4], a1[5], a1[6]};
+    for (int m = 0; m < 4; ++m) P.q1[m] = q1[m];
+    for (int m = 0; m < 3; ++m) P.t1[m] = t1[m];
+    // PoseInverse + QuaternionToRotation (pose1_stage), t_inv (pose1_world)
+    Pose1Stage s;
+    pose1_stage(q1, zero, s);
+    {
+      const double sc = 1.0 / sqrt(q1[0] * q1[0] + q1[1] * q1[1] + q1[2] * q1[2] + q1[3] * q1[3]);
+      const double qi[4] = {sc * q1[0], -(sc * q1[1]), -(sc * q1[2]), -(sc * q1[3])};
+      // quat_rotate_point(qi, .) normalisation
+      const double scale = 1.0 / sqrt(qi[0] * qi[0] + qi[1] * qi[1] + qi[2] * qi[2] + qi[3] * qi[3]);
+      for (int m = 0; m < 4; ++m) P.uqi[m] = scale * qi[m];
+    }
+    P.ti[0] = -(s.R[0] * t1[0] + s.R[1] * t1[1] + s.R[2] * t1[2]);
+    P.ti[1] = -(s.R[3] * t1[0] + s.R[4] * t1[1] + s.R[5] * t1[2]);
+    P.ti[2] = -(s.R[6] * t1[0] + s.R[7] * t1[1] + s.R[8] * t1[2]);
+    P.var1 = pr.var1;
+    P.mask1 = (img_flags[pr.i] >> 1) & 7u;
+    stencil_bounds(q1, t1, rel_step, &P.rho1, P.dt1);
+  } else if (lane == 29) {
+    const double q2[4] = {a2[0], a2[1], a2[2], a2[3]}, t2[3] = {a2[4], a2[5], a2[6]};
+    for (int m = 0; m < 4; ++m) P.q2[m] = q2[m];
+    for (int m = 0; m < 3; ++m) P.t2[m] = t2[m];
+    double u2[4], R2[9];
+    unit_quat(q2, u2);
+    unit_quat_matrix(u2, R2);
+    for (int m = 0; m < 4; ++m) P.u2[m] = u2[m];
+    for (int m = 0; m < 9; ++m) P.R2[m] = R2[m];
+    const double* K = cam + 8 * (size_t)img_cam[pr.j];
+    for (int m = 0; m < 8; ++m) P.K2[m] = K[m];
+    P.var2 = pr.var2;
+    P.mask2 = (img_flags[pr.j] >> 1) & 7u;
+    const uint32_t slot = raster_slot[pr.j];
+    P.slot = slot;
+    const SlotInfo si = slots[slot];
+    P.H2 = (uint32_t)si.H;
+    P.W2 = (uint32_t)si.W;
+    P.TW2 = (uint32_t)si.TW;
+    P.roff = si.off;
+    P.toff = si.toff;
+    stencil_bounds(q2, t2, rel_step, &P.rho2, P.dt2);
+  } else {
+    const double q1[4] = {a1[0], a1[1], a1[2], a1[3]}, q2[4] = {a2[0], a2[1], a2[2], a2[3]};
+    Pose1Stage s;
+    pose1_stage(q1, zero, s);
+    double u2[4], R2[9];
+    unit_quat(q2, u2);
+    unit_quat_matrix(u2, R2);
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c)
+        P.C[3 * r + c] = R2[3 * r] * s.R[c] + R2[3 * r + 1] * s.R[3 + c] + R2[3 * r + 2] * s.R[6 + c];
+  }
 }
 
 // Two pairs per 64-lane workgroup; workgroup 0 also clears the deferred
@@ -560,7 +588,7 @@ struct PrepArgs {
 };
 
 template <int U>
-__global__ __launch_bounds__(256) void step_prologue_kernel(PrepArgs a, int nprep, DevProblem p,
+__global__ __launch_bounds__(256, 8) void step_prologue_kernel(PrepArgs a, int nprep, DevProblem p,
                                                             double* __restrict__ rec, double* __restrict__ zero,
                                                             int nzero, int npack, TouchRanges t, unsigned* sink,
                                                             int nwarm) {
@@ -1924,7 +1952,108 @@ __device__ __forceinline__ bool stencil_group(const SemArgs& a, const PairConst*
 // 64 threads then write J and the scaled rows, 90 threads the chunk's sums in
 // row order into the slots the one-wave kernel fills: the values are its
 // values bit for bit.  Barriers only.
+// One chunk of the four-wave kernel: ch = (pair, first entry), cnt the pair's
+// deferred count, n / smp the lane's sample (read by the caller, lanes with
+// ch.y + lane < cnt only).  Workgroup-uniform exit for a chunk past the count.
 template <int M>
+__device__ __forceinline__ void deferred_waves_chunk(const SemArgs& ak, const PairConst* __restrict__ pcs,
+                                                     const uint32_t* __restrict__ pair_chunk0,
+                                                     double* __restrict__ cpart, double* __restrict__ J_out,
+                                                     int write_samples, int32_t* __restrict__ status_out,
+                                                     double* sraw, double* ssc, double* srs, double* sJ,
+                                                     uint8_t* sredo, int tid, int lane, int wv, uint2 ch,
+                                                     uint32_t cnt, int64_t n, const SemSample& smp) {
+  if (ch.y >= cnt) return;  // workgroup-uniform
+  const PairConst* __restrict__ P = pcs + ch.x;
+  const SemArgs a = with_pair(ak, P);
+  const uint32_t k = ch.y + lane;
+  const float2* dl2 = a.dl + P->roff;
+  const double* K2 = P->K2;
+  double col[3] = {0.0, 0.0, 0.0};
+  bool redone = false;
+  if (k < cnt) {
+    Centre c;
+    if (wv == 0) {
+      centre_geometry<M>(P, smp, K2, c);
+      if (P->var1) redone = stencil_group<M, 0>(a, P, c, smp, K2, dl2, col);
+    } else if (wv == 1) {
+      centre_geometry<M>(P, smp, K2, c);
+      if (P->var1) redone = stencil_group<M, 1>(a, P, c, smp, K2, dl2, col);
+    } else if (wv == 2) {
+      centre_geometry<M>(P, smp, K2, c);
+      if (P->var2) redone = stencil_group<M, 2>(a, P, c, smp, K2, dl2, col);
+    } else {
+      centre_eval<M, true>(a, P, smp, K2, dl2, c);
+      if (P->var2) redone = stencil_group<M, 3>(a, P, c, smp, K2, dl2, col);
+      double rho[3];
+      loss_eval(a.loss_type, a.loss_scale, c.r * c.r, rho);
+      const double sc = sqrt(a.weight * rho[1]);
+      ssc[lane] = sc;
+      srs[lane] = c.r * sc;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 3; ++q) sraw[lane * 12 + 3 * wv + q] = col[q];
+  sredo[wv * 64 + lane] = redone ? 1 : 0;
+  __syncthreads();
+  if (tid < 64) {
+    double rowv[kSemRow];
+#pragma unroll
+    for (int q = 0; q < kSemRow; ++q) rowv[q] = 0.0;
+    if (k < cnt) {
+      double Jt[12];
+#pragma unroll
+      for (int m = 0; m < 12; ++m) Jt[m] = sraw[lane * 12 + m];
+      if ((write_samples & 4) && status_out && (sredo[lane] | sredo[64 + lane] | sredo[128 + lane] | sredo[192 + lane]))
+        status_out[n] += 0x10000;  // diagnostic
+      if (write_samples) {
+        double2* jo = reinterpret_cast<double2*>(J_out + 12 * n);
+#pragma unroll
+        for (int m = 0; m < 6; ++m) jo[m] = make_double2(Jt[2 * m], Jt[2 * m + 1]);
+      }
+      const double sc = ssc[lane];
+#pragma unroll
+      for (int m = 0; m < 12; ++m) rowv[m] = Jt[m] * sc;
+      rowv[12] = srs[lane];
+    }
+#pragma unroll
+    for (int q = 0; q < kSemRow; ++q) sJ[lane * kSemRow + q] = rowv[q];
+  }
+  __syncthreads();
+  const int rows = min(64, (int)(cnt - ch.y));
+  if (tid < kPairVals) {
+    const int e = tid;
+    int ca, cb;
+    if (e < 78) {
+      int a_ = 0, rem = e;
+      while (rem >= 12 - a_) { rem -= 12 - a_; ++a_; }
+      ca = a_;
+      cb = a_ + rem;
+    } else {
+      ca = e - 78;
+      cb = 12;
+    }
+    double acc = 0.0;
+    for (int q = 0; q < rows; ++q) acc += sJ[q * kSemRow + ca] * sJ[q * kSemRow + cb];
+    // the chunk's J'J / J'r, summed per pair in chunk order (pair_reduce_kernel)
+    cpart[((size_t)pair_chunk0[ch.x] + ch.y / 64) * kPairVals + e] = acc;
+  }
+  // no third barrier: sraw / ssc / srs / sredo are last read before the
+  // second barrier, and the next chunk writes sJ only after its first
+  // barrier, which no thread passes before the sums above are formed
+}
+
+// PIPE ("semantic_deferred_pipeline" 1; the resident grid over the compacted
+// list only): the loop's loads run ahead of the chunk being computed.  The
+// list carries each chunk's pair count and pair start beside it (cext, written
+// with the list), so a chunk's record, its lanes' dlist entries and their
+// samples are three dependent loads instead of four; iteration ci issues the
+// record of chunk ci + 3 stride, the entries of ci + 2 stride and the samples
+// of ci + stride before it computes chunk ci, whose own three arrived during
+// the iterations before.  Every index is guarded by the list's length and the
+// pair's count: nothing is read past either.  The chunk itself is computed as
+// before from the same values.
+template <int M, bool PIPE = false>
 __global__ __launch_bounds__(256) void semantic_deferred_waves_kernel(SemArgs ak, const uint2* __restrict__ chunks,
                                                                      const uint32_t* __restrict__ ccount,
                                                                      const PairConst* __restrict__ pcs,
@@ -1933,7 +2062,8 @@ __global__ __launch_bounds__(256) void semantic_deferred_waves_kernel(SemArgs ak
                                                                      const uint32_t* __restrict__ pair_chunk0,
                                                                      double* __restrict__ cpart,
                                                                      double* __restrict__ J_out, int write_samples,
-                                                                     int32_t* __restrict__ status_out = nullptr) {
+                                                                     int32_t* __restrict__ status_out = nullptr,
+                                                                     const uint2* __restrict__ cext = nullptr) {
   __shared__ double sraw[64 * 12];      // raw tangent columns, 3 per wave
   __shared__ double ssc[64], srs[64];   // corrector scale, scaled residual
   __shared__ double sJ[64 * kSemRow];   // scaled rows
@@ -1942,91 +2072,59 @@ __global__ __launch_bounds__(256) void semantic_deferred_waves_kernel(SemArgs ak
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t nch = ccount ? *ccount : blockIdx.x + 1;
   const uint32_t stride = ccount ? gridDim.x : 1u;
-  for (uint32_t ci = blockIdx.x; ci < nch; ci += stride) {
-    const uint2 ch = chunks[ci];  // (pair, first entry)
-    const uint32_t cnt = pair_cnt[ch.x];
-    if (ch.y >= cnt) continue;  // workgroup-uniform
-    const PairConst* __restrict__ P = pcs + ch.x;
-    const SemArgs a = with_pair(ak, P);
-    const uint32_t k = ch.y + lane;
-    const uint32_t pstart = a.pairs[ch.x].start;
-    const float2* dl2 = a.dl + P->roff;
-    const double* K2 = P->K2;
-    double col[3] = {0.0, 0.0, 0.0};
-    bool redone = false;
-    int64_t n = 0;
-    if (k < cnt) {
-      n = (int64_t)pstart + dlist[pstart + k];
-      const SemSample smp = a.samples[n];
-      Centre c;
-      if (wv == 0) {
-        centre_geometry<M>(P, smp, K2, c);
-        if (P->var1) redone = stencil_group<M, 0>(a, P, c, smp, K2, dl2, col);
-      } else if (wv == 1) {
-        centre_geometry<M>(P, smp, K2, c);
-        if (P->var1) redone = stencil_group<M, 1>(a, P, c, smp, K2, dl2, col);
-      } else if (wv == 2) {
-        centre_geometry<M>(P, smp, K2, c);
-        if (P->var2) redone = stencil_group<M, 2>(a, P, c, smp, K2, dl2, col);
-      } else {
-        centre_eval<M, true>(a, P, smp, K2, dl2, c);
-        if (P->var2) redone = stencil_group<M, 3>(a, P, c, smp, K2, dl2, col);
-        double rho[3];
-        loss_eval(a.loss_type, a.loss_scale, c.r * c.r, rho);
-        const double sc = sqrt(a.weight * rho[1]);
-        ssc[lane] = sc;
-        srs[lane] = c.r * sc;
-      }
+  if constexpr (PIPE) {
+    const uint2 none = make_uint2(0u, 0u);
+    // chunk c's record: (pair, first entry), (pair's count, pair's start); zeros past the list
+    auto uniform = [](uint2 v) {  // workgroup-uniform values, kept in scalar registers across the loop
+      return make_uint2((uint32_t)__builtin_amdgcn_readfirstlane((int)v.x),
+                        (uint32_t)__builtin_amdgcn_readfirstlane((int)v.y));
+    };
+    auto record = [&](uint32_t c, uint2& ch, uint2& ex) {
+      ch = uniform(c < nch ? chunks[c] : none);
+      ex = uniform(c < nch ? cext[c] : none);
+    };
+    // the lane's entry of chunk c (the sample's offset in its pair), lanes inside the pair's count only
+    auto entry = [&](uint32_t c, uint2 ch, uint2 ex) -> uint32_t {
+      return c < nch && ch.y + lane < ex.x ? dlist[ex.y + ch.y + lane] : 0u;
+    };
+    auto sample = [&](uint32_t c, uint2 ch, uint2 ex, uint32_t e) -> SemSample {
+      SemSample smp = {{0.0, 0.0, 0.0}, 0.f, 0u};
+      if (c < nch && ch.y + lane < ex.x) smp = ak.samples[(int64_t)ex.y + e];
+      return smp;
+    };
+    uint32_t ci = blockIdx.x;
+    uint2 ch0, ex0, ch1, ex1, ch2, ex2;
+    record(ci, ch0, ex0);
+    record(ci + stride, ch1, ex1);
+    record(ci + 2 * stride, ch2, ex2);
+    uint32_t e0 = entry(ci, ch0, ex0), e1 = entry(ci + stride, ch1, ex1);
+    SemSample s0 = sample(ci, ch0, ex0, e0);
+    for (; ci < nch; ci += stride) {
+      uint2 ch3, ex3;
+      record(ci + 3 * stride, ch3, ex3);
+      const uint32_t e2 = entry(ci + 2 * stride, ch2, ex2);
+      const SemSample s1 = sample(ci + stride, ch1, ex1, e1);
+      deferred_waves_chunk<M>(ak, pcs, pair_chunk0, cpart, J_out, write_samples, status_out, sraw, ssc, srs, sJ, sredo,
+                              tid, lane, wv, ch0, ex0.x, (int64_t)ex0.y + e0, s0);
+      ch0 = ch1, ex0 = ex1, e0 = e1, s0 = s1;
+      ch1 = ch2, ex1 = ex2, e1 = e2;
+      ch2 = ch3, ex2 = ex3;
     }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) sraw[lane * 12 + 3 * wv + q] = col[q];
-    sredo[wv * 64 + lane] = redone ? 1 : 0;
-    __syncthreads();
-    if (tid < 64) {
-      double rowv[kSemRow];
-#pragma unroll
-      for (int q = 0; q < kSemRow; ++q) rowv[q] = 0.0;
-      if (k < cnt) {
-        double Jt[12];
-#pragma unroll
-        for (int m = 0; m < 12; ++m) Jt[m] = sraw[lane * 12 + m];
-        if ((write_samples & 4) && status_out && (sredo[lane] | sredo[64 + lane] | sredo[128 + lane] | sredo[192 + lane]))
-          status_out[n] += 0x10000;  // diagnostic
-        if (write_samples) {
-          double2* jo = reinterpret_cast<double2*>(J_out + 12 * n);
-#pragma unroll
-          for (int m = 0; m < 6; ++m) jo[m] = make_double2(Jt[2 * m], Jt[2 * m + 1]);
-        }
-        const double sc = ssc[lane];
-#pragma unroll
-        for (int m = 0; m < 12; ++m) rowv[m] = Jt[m] * sc;
-        rowv[12] = srs[lane];
+  } else {
+    for (uint32_t ci = blockIdx.x; ci < nch; ci += stride) {
+      const uint2 ch = chunks[ci];  // (pair, first entry)
+      const uint32_t cnt = pair_cnt[ch.x];
+      if (ch.y >= cnt) continue;  // workgroup-uniform
+      const uint32_t pstart = ak.pairs[ch.x].start;
+      int64_t n = 0;
+      SemSample smp = {{0.0, 0.0, 0.0}, 0.f, 0u};
+      if (ch.y + lane < cnt) {
+        n = (int64_t)pstart + dlist[pstart + ch.y + lane];
+        smp = ak.samples[n];
       }
-#pragma unroll
-      for (int q = 0; q < kSemRow; ++q) sJ[lane * kSemRow + q] = rowv[q];
+      deferred_waves_chunk<M>(ak, pcs, pair_chunk0, cpart, J_out, write_samples, status_out, sraw, ssc, srs, sJ, sredo,
+                              tid, lane, wv, ch, cnt, n, smp);
     }
-    __syncthreads();
-    const int rows = min(64, (int)(cnt - ch.y));
-    if (tid < kPairVals) {
-      const int e = tid;
-      int ca, cb;
-      if (e < 78) {
-        int a_ = 0, rem = e;
-        while (rem >= 12 - a_) { rem -= 12 - a_; ++a_; }
-        ca = a_;
-        cb = a_ + rem;
-      } else {
-        ca = e - 78;
-        cb = 12;
-      }
-      double acc = 0.0;
-      for (int q = 0; q < rows; ++q) acc += sJ[q * kSemRow + ca] * sJ[q * kSemRow + cb];
-      // the chunk's J'J / J'r, summed per pair in chunk order (pair_reduce_kernel)
-      cpart[((size_t)pair_chunk0[ch.x] + ch.y / 64) * kPairVals + e] = acc;
-    }
-    // no third barrier: sraw / ssc / srs / sredo are last read before the
-    // second barrier, and the next chunk writes sJ only after its first
-    // barrier, which no thread passes before the sums above are formed
   }
 }
 
@@ -2045,6 +2143,8 @@ __global__ __launch_bounds__(256) void semantic_deferred_waves_kernel(SemArgs ak
 // every workgroup sums ceil(pair_cnt[q] / 64) over those pairs itself, so no
 // workgroup waits for another and the list is pair-major, the same run to
 // run.  The model's last pair writes the list's length dcount[model].
+// dext (nullable): the same places of a second list take (pair_cnt[p],
+// pairs[p].start), what the pipelined deferred loop reads per chunk.
 template <bool COMPACT>
 __global__ __launch_bounds__(256) void deferred_order_kernel(const unsigned long long* __restrict__ dmask,
                                                              const uint32_t* __restrict__ pair_tile0,
@@ -2054,7 +2154,8 @@ __global__ __launch_bounds__(256) void deferred_order_kernel(const unsigned long
                                                              const uint4* __restrict__ ord = nullptr,
                                                              const uint32_t* __restrict__ mlist = nullptr,
                                                              uint2* __restrict__ dchunks = nullptr,
-                                                             uint32_t* __restrict__ dcount = nullptr) {
+                                                             uint32_t* __restrict__ dcount = nullptr,
+                                                             uint2* __restrict__ dext = nullptr) {
   __shared__ uint32_t sc[256];
   __shared__ uint32_t spre[4];
   const int p = blockIdx.x, tid = threadIdx.x;
@@ -2094,6 +2195,9 @@ __global__ __launch_bounds__(256) void deferred_order_kernel(const unsigned long
     const uint32_t nch = (base + 63) / 64;  // base = pair_cnt[p], the flat pass's count
     uint2* out = dchunks + od.w + pre;
     for (uint32_t c = tid; c < nch; c += 256) out[c] = make_uint2((uint32_t)p, 64 * c);
+    // "semantic_deferred_pipeline": (the pair's count, its start) beside each chunk
+    if (dext)
+      for (uint32_t c = tid; c < nch; c += 256) dext[od.w + pre + c] = make_uint2(base, pr.start);
     if (tid == 0 && (od.z >> 31)) dcount[od.z & 0x7fffffffu] = pre + nch;
   } else {
     if (tid == 0) pair_cnt[p] = base;
@@ -2128,7 +2232,9 @@ constexpr int kOrderCompactMaxPairs = 4096;
 
 __global__ __launch_bounds__(256) void deferred_compact_kernel(const uint2* __restrict__ chunks, int nchunks,
                                                                const uint32_t* __restrict__ pair_cnt, ModelRanges mr,
-                                                               uint2* __restrict__ out, uint32_t* __restrict__ cnt) {
+                                                               uint2* __restrict__ out, uint32_t* __restrict__ cnt,
+                                                               const SemPair* __restrict__ pairs = nullptr,
+                                                               uint2* __restrict__ ext = nullptr) {
   // one atomic per workgroup and model: per-wave counts through LDS, the
   // workgroup's base per model, then each wave's offset inside it
   __shared__ uint32_t swc[4][kNumModels];
@@ -2137,11 +2243,13 @@ __global__ __launch_bounds__(256) void deferred_compact_kernel(const uint2* __re
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const bool valid = i < nchunks;
   uint2 ch = make_uint2(0u, 0u);
+  uint32_t pcnt = 0;
   int m = 0;
   bool live = false;
   if (valid) {
     ch = chunks[i];
-    live = ch.y < pair_cnt[ch.x];
+    pcnt = pair_cnt[ch.x];
+    live = ch.y < pcnt;
     while (m + 1 < kNumModels && i >= mr.b[m + 1]) ++m;
   }
   uint32_t rank = 0;  // the lane's rank among its wave's live chunks of its model
@@ -2161,6 +2269,8 @@ __global__ __launch_bounds__(256) void deferred_compact_kernel(const uint2* __re
     uint32_t off = sbase[m];
     for (int w = 0; w < wv; ++w) off += swc[w][m];
     out[mr.b[m] + off + rank] = ch;
+    // "semantic_deferred_pipeline": (the pair's count, its start) beside the chunk
+    if (ext) ext[mr.b[m] + off + rank] = make_uint2(pcnt, pairs[ch.x].start);
   }
 }
 
@@ -2661,6 +2771,7 @@ mi_ba_status semantic_create(mi_ba_context* ctx, const mi_ba_semantic* sem) {
   }
   if (S->pair_cnt.alloc(std::max(1, S->npairs)) || S->dlist.alloc(std::max<int64_t>(1, S->ns)) ||
       S->chunks.alloc(std::max<size_t>(1, chunks.size())) || S->dchunks.alloc(std::max<size_t>(1, chunks.size())) ||
+      S->dext.alloc(std::max<size_t>(1, chunks.size())) ||
       S->dcount.alloc(kNumModels))
     return MI_BA_ERR_OUT_OF_MEMORY;
   // deterministic sums (see SemanticState)
@@ -2745,7 +2856,12 @@ mi_ba_status semantic_create(mi_ba_context* ctx, const mi_ba_semantic* sem) {
                 hipSuccess ||
             nb <= 0)
           nb = 4;
-        S->dwaves_blocks[model] = nb;
+        S->dwaves_blocks[0][model] = nb;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, semantic_deferred_waves_kernel<M, true>, 256, 0) !=
+                hipSuccess ||
+            nb <= 0)
+          nb = 4;
+        S->dwaves_blocks[1][model] = nb;  // the pipelined loop ("semantic_deferred_pipeline")
       });
     }
   }
@@ -2990,12 +3106,20 @@ mi_ba_status semantic_linearize(mi_ba_context* ctx, double* d_cost, bool write_s
   const bool split = deferred_stream != nullptr && ctx->sem_variant == 6;
   if (ctx->sem_variant == 6) {
     const int ws = write_samples ? 1 | (ctx->sem_diag ? 2 : 0) | (ctx->sem_diag == 2 ? 4 : 0) : 0;
+    // "semantic_deferred_pipeline": the four-wave kernel's resident loop reads
+    // ahead; the list kernels write each chunk's pair count and start (dext)
+    const bool pipe = ctx->sem_dpipe != 0 && ctx->sem_compact != 0 && ctx->sem_dwaves == 4 && !ctx->sem_deferred_box
+#ifdef MI_BA_AB_VARIANTS
+                      && ctx->sem_dvar == 0
+#endif
+        ;
+    uint2* dext = pipe ? S->dext.ptr : nullptr;
     auto deferred = [&](hipStream_t ds) -> mi_ba_status {
       // each pair's deferred samples in sample order (pair_cnt, dlist)
       if (order_compact)
         hipLaunchKernelGGL(deferred_order_kernel<true>, dim3(S->npairs), dim3(256), 0, ds, S->dmask.ptr,
                            S->pair_tile0.ptr, S->pairs.ptr, S->pair_cnt.ptr, S->dlist.ptr, S->pair_ord.ptr,
-                           S->model_pairs.ptr, S->dchunks.ptr, S->dcount.ptr);
+                           S->model_pairs.ptr, S->dchunks.ptr, S->dcount.ptr, dext);
       else
         hipLaunchKernelGGL(deferred_order_kernel<false>, dim3(S->npairs), dim3(256), 0, ds, S->dmask.ptr,
                            S->pair_tile0.ptr, S->pairs.ptr, S->pair_cnt.ptr, S->dlist.ptr);
@@ -3007,7 +3131,8 @@ mi_ba_status semantic_linearize(mi_ba_context* ctx, double* d_cost, bool write_s
         for (int m = 0; m <= kNumModels; ++m) mr.b[m] = S->model_chunks[m];
         // dcount was zeroed by the pair prep kernel (ordered before the flat pass)
         hipLaunchKernelGGL(deferred_compact_kernel, dim3((unsigned)((nall + 255) / 256)), dim3(256), 0, ds,
-                           S->chunks.ptr, nall, S->pair_cnt.ptr, mr, S->dchunks.ptr, S->dcount.ptr);
+                           S->chunks.ptr, nall, S->pair_cnt.ptr, mr, S->dchunks.ptr, S->dcount.ptr, S->pairs.ptr,
+                           dext);
       }
       for (int model = 0; model < kNumModels; ++model) {
         const int c0 = S->model_chunks[model], nc = S->model_chunks[model + 1] - c0;
@@ -3029,14 +3154,21 @@ mi_ba_status semantic_linearize(mi_ba_context* ctx, double* d_cost, bool write_s
                             && ctx->sem_dvar == 0
 #endif
             ;
-        const int per_cu = waves4 && !ctx->sem_dgrid_set ? std::max(1, S->dwaves_blocks[model])
+        const int per_cu = waves4 && !ctx->sem_dgrid_set ? std::max(1, S->dwaves_blocks[pipe ? 1 : 0][model])
                                                          : std::max(1, ctx->sem_dgrid);
-        const int grid = compact ? std::min(nc, per_cu * S->n_cu) : nc;
+        // "semantic_deferred_groups": the resident grid in workgroups (tests: a
+        // few workgroups walk a small scene's whole list)
+        const int resident = ctx->sem_dgroups > 0 ? ctx->sem_dgroups : per_cu * S->n_cu;
+        const int grid = compact ? std::min(nc, resident) : nc;
         const uint2* list = (compact ? S->dchunks.ptr : S->chunks.ptr) + c0;
         const uint32_t* count = compact ? S->dcount.ptr + model : nullptr;
         dispatch_model(model, [&](auto m) {
           constexpr int M = decltype(m)::value;
-          if (waves4)
+          if (waves4 && pipe)
+            hipLaunchKernelGGL((semantic_deferred_waves_kernel<M, true>), dim3(grid), dim3(256), 0, ds, a, list, count,
+                               pcs, S->pair_cnt.ptr, S->dlist.ptr, S->pair_chunk0.ptr, S->cpart.ptr, S->J.ptr, ws,
+                               S->status.ptr, dext + c0);
+          else if (waves4)
             hipLaunchKernelGGL((semantic_deferred_waves_kernel<M>), dim3(grid), dim3(256), 0, ds, a, list, count,
                                pcs, S->pair_cnt.ptr, S->dlist.ptr, S->pair_chunk0.ptr, S->cpart.ptr, S->J.ptr, ws,
                                S->status.ptr);

@@ -41,8 +41,6 @@ __device__ inline void pack_image_record(const DevProblem& p, double* __restrict
   for (int m = 0; m < 7; ++m) o[m] = p.qt[8 * (size_t)k + m];
   o[7] = __longlong_as_double(
       (long long)(p.img_flags[k] | ((p.cam_var[cam] != 0 ? 1u : 0u) << 8) | ((uint32_t)p.cam_model[cam] << 16)));
-#pragma unroll
-  for (int m = 0; m < 8; ++m) o[8 + m] = p.cam[8 * (size_t)cam + m];
   const double q[4] = {o[0], o[1], o[2], o[3]};
   double R[9];
   unit_quat_matrix_contracted(q, R);
@@ -51,6 +49,9 @@ __device__ inline void pack_image_record(const DevProblem& p, double* __restrict
   o[25] = fabs(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] - 1.0) <= 1e-12 ? 1.0 : 0.0;
 #pragma unroll
   for (int m = 26; m < kImgRec; ++m) o[m] = 0.0;
+  // the camera's parameters last: copied when the rotation's registers are free
+#pragma unroll
+  for (int m = 0; m < 8; ++m) o[8 + m] = p.cam[8 * (size_t)cam + m];
 }
 
 // The input warm-up's ranges (launch_touch_inputs): 16-B words of each.
