@@ -579,6 +579,14 @@ mi_ba_status mi_ba_context_set_host_reducer(mi_ba_context* ctx, int32_t rank, in
  *                           1 pair tables + image records + input warm-up in one launch,
  *                           2 deferred chunk list laid out by the ordering kernel,
  *                           4 pair blocks in the cost sums' launch; default 1, 0 off
+ *   "semantic_pair_fused"   1: one workgroup per image pair runs the pair's flat pass, its
+ *                           deferred-sample pass and its block sum in one launch per camera
+ *                           model (same results bit for bit), where the step writes no
+ *                           samples and the pairs fill the chip ("semantic_pair_min_pairs":
+ *                           the fewest pairs, -1 = CUs x resident workgroups per CU;
+ *                           "semantic_pair_list_cap": deferred-list entries kept in LDS);
+ *                           0 (default): the flat pass, list kernels, deferred pass and
+ *                           pair sums as separate launches
  *   "semantic_flat_coarse"  the flat pass's pixel box from a rotation and a translation
  *                           group of the stencil classes: 2 (default) with the camera
  *                           model's Jacobian at the centre, 1 with |A| bounded from the

@@ -122,6 +122,13 @@ struct mi_ba_context {
                          // record, entries and samples one to three chunks ahead (chunk records carry the
                          // pair's count and start), 0 every chunk loads its own before it computes (default:
                          // 1 measured no gain, profiles/dp_ab_deferred_pipeline.jsonl)
+  int sem_pair_fused = 0;  // "semantic_pair_fused": 1 one workgroup per pair runs the pair's flat test, its stencil
+                           // chunks and its block sum (semantic_pair_kernel), 0 the five-kernel route (default:
+                           // 1 measured no gain, profiles/pf_bench_pair_fused.jsonl)
+  int sem_pair_min = -1;   // "semantic_pair_min_pairs": fewest pairs the fused route takes (-1: a resident grid's
+                           // worth, from the occupancy query; tests set 0)
+  int sem_pair_cap = 1 << 30;  // "semantic_pair_list_cap": the fused kernel's list entries kept in LDS (clamped to
+                               // kSemPairListCap; tests set a small one: the rest goes through dlist)
   int sem_dgroups = 0;   // "semantic_deferred_groups": the deferred pass's resident grid in workgroups
                          // (0: per CU, sem_dgrid / the occupancy query)
   int sem_dvar = 0;      // "semantic_deferred_variant" (tools build): stencil batch / occupancy variants

@@ -2483,6 +2483,23 @@ mi_ba_status mi_ba_set_tuning(mi_ba_context* ctx, const char* key, int32_t value
     ctx->sem_dpipe = value;
     return MI_BA_OK;
   }
+  // 1: one workgroup per pair runs the pair's flat test, stencil chunks and
+  // block sum (where semantic_linearize says the route applies), 0: the
+  // five-kernel route
+  if (std::strcmp(key, "semantic_pair_fused") == 0 && (value == 0 || value == 1)) {
+    ctx->sem_pair_fused = value;
+    return MI_BA_OK;
+  }
+  // fewest pairs the fused route takes (-1: a resident grid's worth)
+  if (std::strcmp(key, "semantic_pair_min_pairs") == 0 && value >= -1) {
+    ctx->sem_pair_min = value;
+    return MI_BA_OK;
+  }
+  // the fused kernel's deferred-list entries kept in LDS (at most kSemPairListCap)
+  if (std::strcmp(key, "semantic_pair_list_cap") == 0 && value >= 0) {
+    ctx->sem_pair_cap = value;
+    return MI_BA_OK;
+  }
   // the deferred pass's resident grid in workgroups (0: sized per CU)
   if (std::strcmp(key, "semantic_deferred_groups") == 0 && value >= 0 && value <= (1 << 20)) {
     ctx->sem_dgroups = value;

@@ -44,6 +44,12 @@ struct SlotInfo {
   int32_t H, W, TW, pad;
 };
 
+// "semantic_pair_fused": LDS entries of a workgroup's deferred list
+// (semantic_pair_kernel; 4 KB beside the stencil's 14 KB, so the registers and
+// not the LDS bound the workgroups per CU).  A C4 pair defers about 230 of its
+// 2 500 samples; a longer list continues in the pair's dlist region.
+constexpr int kSemPairListCap = 1024;
+
 struct SemanticState {
   std::vector<int32_t> img_h, img_w;       // [I] each image's raster size
   std::vector<SlotInfo> slots_host;        // [nslots]
@@ -96,6 +102,9 @@ struct SemanticState {
   DevArray<uint32_t> model_pairs;          // each model's pairs in pair order (model-major)
   DevArray<uint4> pair_ord;                // [npairs] the pair's model list begin, its place in model_pairs,
                                            // model | last-of-model << 31, model_chunks[model]
+  int model_pair0[kNumModels + 1] = {};    // each model's range of model_pairs
+  int pair_blocks[kNumModels] = {};        // resident semantic_pair_kernel workgroups per CU (occupancy query of
+                                           // the label-plane form), per model ("semantic_pair_fused")
   bool order_compact = false;              // no model has more pairs than deferred_order_kernel<true> takes
   int n_cu = 256;                          // compute units (the deferred pass's resident grid)
   int dwaves_blocks[2][kNumModels] = {};   // resident four-wave deferred workgroups per CU (occupancy query), per

@@ -1591,6 +1591,134 @@ __device__ __forceinline__ int tile_depth_side(const SemArgs& a, const FlatBox& 
   return 0;
 }
 
+// The flat pass's per-sample body (semantic_flat_kernel and
+// semantic_pair_kernel): the centre outcome c.r / c.st of sample smp of pair
+// P, whether the flat test left the sample to the deferred pass, whether
+// both were settled without the rasters (diagnostic), and the sample's cost
+// (returned).  spal: the label palette in LDS (LP).
+template <int M, bool WS, bool LP, int COARSE>
+__device__ __forceinline__ double flat_sample(const SemArgs& a, const PairConst* __restrict__ P, const double* K2,
+                                              const float2* dl2, const float* spal, const SemSample& smp, Centre& c,
+                                              bool& deferred, bool& decided) {
+  deferred = false;
+  // centre geometry (reference sequence, as centre_eval / project_centre)
+  double rot[3];
+  unit_quat_rotate(P->uqi, smp.pc1, rot);
+  c.pw[0] = rot[0] + P->ti[0];
+  c.pw[1] = rot[1] + P->ti[1];
+  c.pw[2] = rot[2] + P->ti[2];
+  double rot2[3];
+  unit_quat_rotate(P->u2, c.pw, rot2);
+  c.p2[0] = rot2[0] + P->t2[0];
+  c.p2[1] = rot2[1] + P->t2[1];
+  c.p2[2] = rot2[2] + P->t2[2];
+  c.mag = fabs(smp.pc1[0]) + fabs(smp.pc1[1]) + fabs(smp.pc1[2]) + fabs(P->t1[0]) + fabs(P->t1[1]) +
+          fabs(P->t1[2]) + fabs(c.pw[0]) + fabs(c.pw[1]) + fabs(c.pw[2]) + fabs(P->t2[0]) + fabs(P->t2[1]) +
+          fabs(P->t2[2]);
+  c.w[0] = smp.pc1[0] - P->t1[0];
+  c.w[1] = smp.pc1[1] - P->t1[1];
+  c.w[2] = smp.pc1[2] - P->t1[2];
+  const double u2 = c.p2[0] / c.p2[2];
+  const double v2 = c.p2[1] / c.p2[2];
+  double x2, y2;
+  world_to_image<M>(K2, u2, v2, &x2, &y2);
+  const int cpx = cast_to_int_x86(round(x2));
+  const int cpy = cast_to_int_x86(round(y2));
+  const bool cin = !(cpx < 0 || cpx >= a.W || cpy < 0 || cpy >= a.H);
+  FlatBox fb;
+  const bool cand = COARSE == 3   ? flat_box_coarse<M, false, true>(P, c, K2, u2, v2, x2, y2, fb)
+                    : COARSE == 2 ? flat_box_coarse<M, true>(P, c, K2, u2, v2, x2, y2, fb)
+                    : COARSE == 1 ? flat_box_coarse<M>(P, c, K2, u2, v2, x2, y2, fb)
+                                  : flat_box<M>(P, c, K2, fb);
+  decided = false;        // the centre outcome and the flat test are settled without the raster
+  bool resolved = false;  // the centre outcome is settled (the flat test may have failed)
+  if constexpr (LP) {
+    // label planes: one 8-B tile depth range (a line shared by the wave's
+    // neighbouring samples) settles the depth test of the whole box; on the
+    // valid side the box's labels come from the 1-B label plane
+    if (cand && fb.x0 >= 0 && fb.y0 >= 0 && fb.x0 + fb.ncol <= a.W && fb.y0 + fb.nrow <= a.H && cpx >= fb.x0 &&
+        cpx < fb.x0 + fb.ncol && cpy >= fb.y0 && cpy < fb.y0 + fb.nrow) {
+      // the tile range and the box's labels requested together (one round
+      // trip; the labels go unused when the depth test settles the box invalid)
+      const float2 dr = a.dtile[P->toff + (size_t)(fb.y0 >> 3) * a.TW + (fb.x0 >> 3)];
+      const uint8_t* lp = a.lab8 + P->roff + (size_t)fb.y0 * a.W + fb.x0;
+      const uint8_t lc = lp[(size_t)(cpy - fb.y0) * a.W + (cpx - fb.x0)];
+      uint8_t L[9];
+#pragma unroll
+      for (int q = 0; q < 9; ++q) L[q] = (q % 3 < fb.ncol && q / 3 < fb.nrow) ? lp[(size_t)(q / 3) * a.W + q % 3] : lc;
+      const int side = tile_depth_side(a, fb, dr, c.p2[2], c.mag);
+      if (side == 2) {
+        c.st = MI_BA_INVALID_DEPTH;
+        c.r = 0.0;
+        decided = resolved = true;
+      } else if (side == 1) {
+        c.st = MI_BA_VALID;
+        c.r = (smp.label1 == spal[lc]) ? 0.0 : 1.0;
+        bool flat = true;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) flat = flat && ((smp.label1 == spal[L[q]]) ? 0.0 : 1.0) == c.r;
+        resolved = true;
+        decided = flat;
+        deferred = !flat;
+      }
+    }
+  }
+  if constexpr (WS) {
+    // one 16-B read of the window holding the box (its top-left pixel)
+    if (!resolved && cand && fb.x0 >= 0 && fb.y0 >= 0 && fb.x0 + 2 < a.W && fb.y0 + 2 < a.H) {
+      const float4 w = a.wsum[P->roff + (size_t)fb.y0 * a.W + fb.x0];
+      decided = resolved = window_decides(a, fb, w, c.p2[2], c.mag, smp.label1, &c.st, &c.r);
+    }
+  }
+  if (!resolved && cand &&
+      (fb.x0 + fb.ncol <= 0 || fb.x0 >= a.W || fb.y0 + fb.nrow <= 0 || fb.y0 >= a.H)) {
+    // every reachable pixel (the centre's among them) lies outside the
+    // raster: the centre and every stencil point are OUT_OF_BOUNDS (f = 0),
+    // the flat test's outcome without a raster read (14 % of C4's samples)
+    c.st = MI_BA_OUT_OF_BOUNDS;
+    c.r = 0.0;
+    decided = resolved = true;
+  }
+  if (!resolved) {
+    // every raster read of the sample in one round trip: the centre pixel and the box
+    const float2 sc = dl2[cin ? cpy * a.W + cpx : 0];
+    float2 s[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) s[q] = dl2[flat_index(a, fb, cand, q)];
+    // centre outcome (semantic_cost_functions.h:141-205)
+    if (!cin) {
+      c.st = MI_BA_OUT_OF_BOUNDS;
+      c.r = 0.0;
+    } else if (fabs((double)sc.x - c.p2[2]) > a.threshold) {
+      c.st = MI_BA_INVALID_DEPTH;
+      c.r = 0.0;
+    } else {
+      c.st = MI_BA_VALID;
+      c.r = (smp.label1 == sc.y) ? 0.0 : 1.0;
+    }
+    deferred = !(cand && flat_check(a, fb, s, c.p2[2], c.mag, smp.label1, c.r));
+  }
+  double rho[3];
+  loss_eval(a.loss_type, a.loss_scale, c.r * c.r, rho);
+  return 0.5 * (a.weight * rho[0]);
+}
+
+// A tile's cost from its threads' (inactive ones: 0): wave shuffle, the four
+// wave sums through sred, summed in wave order by thread 0 into *out.  One
+// barrier; sred is read behind it by thread 0 only.
+__device__ __forceinline__ void tile_cost_sum(double cost, double* sred, int tid, int lane, double* __restrict__ out) {
+  double v = cost;
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if (lane == 0) sred[tid >> 6] = v;
+  __syncthreads();
+  if (tid == 0) {
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) s += sred[w];
+    *out = s;
+  }
+}
+
 template <int M, bool FAST, bool WS = false, bool LP = false, int COARSE = 0>
 __global__ __launch_bounds__(kBlock) void semantic_flat_kernel(SemArgs ak, const SemTile* __restrict__ tiles,
                                                                const PairConst* __restrict__ pcs,
@@ -1619,107 +1747,9 @@ __global__ __launch_bounds__(kBlock) void semantic_flat_kernel(SemArgs ak, const
   }
   if (active) {
     const SemSample smp = a.samples[n];
-    // centre geometry (reference sequence, as centre_eval / project_centre)
     Centre c;
-    double rot[3];
-    unit_quat_rotate(P->uqi, smp.pc1, rot);
-    c.pw[0] = rot[0] + P->ti[0];
-    c.pw[1] = rot[1] + P->ti[1];
-    c.pw[2] = rot[2] + P->ti[2];
-    double rot2[3];
-    unit_quat_rotate(P->u2, c.pw, rot2);
-    c.p2[0] = rot2[0] + P->t2[0];
-    c.p2[1] = rot2[1] + P->t2[1];
-    c.p2[2] = rot2[2] + P->t2[2];
-    c.mag = fabs(smp.pc1[0]) + fabs(smp.pc1[1]) + fabs(smp.pc1[2]) + fabs(P->t1[0]) + fabs(P->t1[1]) +
-            fabs(P->t1[2]) + fabs(c.pw[0]) + fabs(c.pw[1]) + fabs(c.pw[2]) + fabs(P->t2[0]) + fabs(P->t2[1]) +
-            fabs(P->t2[2]);
-    c.w[0] = smp.pc1[0] - P->t1[0];
-    c.w[1] = smp.pc1[1] - P->t1[1];
-    c.w[2] = smp.pc1[2] - P->t1[2];
-    const double u2 = c.p2[0] / c.p2[2];
-    const double v2 = c.p2[1] / c.p2[2];
-    double x2, y2;
-    world_to_image<M>(K2, u2, v2, &x2, &y2);
-    const int cpx = cast_to_int_x86(round(x2));
-    const int cpy = cast_to_int_x86(round(y2));
-    const bool cin = !(cpx < 0 || cpx >= a.W || cpy < 0 || cpy >= a.H);
-    FlatBox fb;
-    const bool cand = COARSE == 3   ? flat_box_coarse<M, false, true>(P, c, K2, u2, v2, x2, y2, fb)
-                      : COARSE == 2 ? flat_box_coarse<M, true>(P, c, K2, u2, v2, x2, y2, fb)
-                      : COARSE == 1 ? flat_box_coarse<M>(P, c, K2, u2, v2, x2, y2, fb)
-                                    : flat_box<M>(P, c, K2, fb);
-    bool decided = false;   // the centre outcome and the flat test are settled without the raster
-    bool resolved = false;  // the centre outcome is settled (the flat test may have failed)
-    if constexpr (LP) {
-      // label planes: one 8-B tile depth range (a line shared by the wave's
-      // neighbouring samples) settles the depth test of the whole box; on the
-      // valid side the box's labels come from the 1-B label plane
-      if (cand && fb.x0 >= 0 && fb.y0 >= 0 && fb.x0 + fb.ncol <= a.W && fb.y0 + fb.nrow <= a.H && cpx >= fb.x0 &&
-          cpx < fb.x0 + fb.ncol && cpy >= fb.y0 && cpy < fb.y0 + fb.nrow) {
-        // the tile range and the box's labels requested together (one round
-        // trip; the labels go unused when the depth test settles the box invalid)
-        const float2 dr = a.dtile[P->toff + (size_t)(fb.y0 >> 3) * a.TW + (fb.x0 >> 3)];
-        const uint8_t* lp = a.lab8 + P->roff + (size_t)fb.y0 * a.W + fb.x0;
-        const uint8_t lc = lp[(size_t)(cpy - fb.y0) * a.W + (cpx - fb.x0)];
-        uint8_t L[9];
-#pragma unroll
-        for (int q = 0; q < 9; ++q) L[q] = (q % 3 < fb.ncol && q / 3 < fb.nrow) ? lp[(size_t)(q / 3) * a.W + q % 3] : lc;
-        const int side = tile_depth_side(a, fb, dr, c.p2[2], c.mag);
-        if (side == 2) {
-          c.st = MI_BA_INVALID_DEPTH;
-          c.r = 0.0;
-          decided = resolved = true;
-        } else if (side == 1) {
-          c.st = MI_BA_VALID;
-          c.r = (smp.label1 == spal[lc]) ? 0.0 : 1.0;
-          bool flat = true;
-#pragma unroll
-          for (int q = 0; q < 9; ++q) flat = flat && ((smp.label1 == spal[L[q]]) ? 0.0 : 1.0) == c.r;
-          resolved = true;
-          decided = flat;
-          deferred = !flat;
-        }
-      }
-    }
-    if constexpr (WS) {
-      // one 16-B read of the window holding the box (its top-left pixel)
-      if (!resolved && cand && fb.x0 >= 0 && fb.y0 >= 0 && fb.x0 + 2 < a.W && fb.y0 + 2 < a.H) {
-        const float4 w = a.wsum[P->roff + (size_t)fb.y0 * a.W + fb.x0];
-        decided = resolved = window_decides(a, fb, w, c.p2[2], c.mag, smp.label1, &c.st, &c.r);
-      }
-    }
-    if (!resolved && cand &&
-        (fb.x0 + fb.ncol <= 0 || fb.x0 >= a.W || fb.y0 + fb.nrow <= 0 || fb.y0 >= a.H)) {
-      // every reachable pixel (the centre's among them) lies outside the
-      // raster: the centre and every stencil point are OUT_OF_BOUNDS (f = 0),
-      // the flat test's outcome without a raster read (14 % of C4's samples)
-      c.st = MI_BA_OUT_OF_BOUNDS;
-      c.r = 0.0;
-      decided = resolved = true;
-    }
-    if (!resolved) {
-      // every raster read of the sample in one round trip: the centre pixel and the box
-      const float2 sc = dl2[cin ? cpy * a.W + cpx : 0];
-      float2 s[9];
-#pragma unroll
-      for (int q = 0; q < 9; ++q) s[q] = dl2[flat_index(a, fb, cand, q)];
-      // centre outcome (semantic_cost_functions.h:141-205)
-      if (!cin) {
-        c.st = MI_BA_OUT_OF_BOUNDS;
-        c.r = 0.0;
-      } else if (fabs((double)sc.x - c.p2[2]) > a.threshold) {
-        c.st = MI_BA_INVALID_DEPTH;
-        c.r = 0.0;
-      } else {
-        c.st = MI_BA_VALID;
-        c.r = (smp.label1 == sc.y) ? 0.0 : 1.0;
-      }
-      deferred = !(cand && flat_check(a, fb, s, c.p2[2], c.mag, smp.label1, c.r));
-    }
-    double rho[3];
-    loss_eval(a.loss_type, a.loss_scale, c.r * c.r, rho);
-    cost = 0.5 * (a.weight * rho[0]);
+    bool decided;
+    cost = flat_sample<M, WS, LP, COARSE>(a, P, K2, dl2, spal, smp, c, deferred, decided);
     if (write_samples) {
       r_out[n] = c.r;
       status_out[n] = c.st + ((write_samples & 2) && deferred ? 0x1000 : 0) + ((write_samples & 4) && decided ? 0x4000 : 0);
@@ -1738,16 +1768,7 @@ __global__ __launch_bounds__(kBlock) void semantic_flat_kernel(SemArgs ak, const
   // deferred samples counted here, integer adds read behind the kernel
   // boundary (deferred_order_kernel<true> lays out the chunk list from them)
   if (pair_cnt && lane == 0 && bal) atomicAdd(pair_cnt + t.pair, (uint32_t)__popcll(bal));
-  double v = cost;
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if (lane == 0) sred[tid >> 6] = v;
-  __syncthreads();
-  if (tid == 0) {
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) s += sred[w];
-    cost_partial[blockIdx.x] = s;
-  }
+  tile_cost_sum(cost, sred, tid, lane, cost_partial + blockIdx.x);
 }
 
 // Pass 2: chunk = 64 consecutive entries of one pair's deferred region
@@ -2212,6 +2233,116 @@ __global__ __launch_bounds__(128) void pair_reduce_kernel(const uint32_t* __rest
                                                           const double* __restrict__ cpart,
                                                           double* __restrict__ pair_blk) {
   pair_block_value(pair_cnt, pair_chunk0, cpart, pair_blk, kPairVals, kPairStride, blockIdx.x, threadIdx.x);
+}
+
+// "semantic_pair_fused" 1: the flat pass, the ordering, the deferred pass and
+// the pair sum of one pair in one 256-thread workgroup (grid = the pairs of
+// model M, mlist their indices in pair order).  A pair's stencil work needs
+// only that pair's flat results, so the workgroup keeps what the five-kernel
+// route hands from kernel to kernel through dmask, pair_cnt, the chunk lists
+// and dcount:
+//   tiles    for each 256-sample tile of the pair in order, flat_sample (lane
+//            = sample) and tile_cost_sum into the tile's cost partial, as
+//            semantic_flat_kernel; the next tile's samples are loaded before
+//            the current tile's arithmetic.  The tile's deferred samples go
+//            behind the list's earlier entries in sample order (tile, wave,
+//            lane: the ballot's prefix count inside the wave, the waves'
+//            counts through LDS), which is deferred_order_kernel's order.
+//   list     entries below cap (<= kSemPairListCap) in LDS, the rest in the
+//            pair's dlist region, which this workgroup alone writes and reads
+//            with a barrier in between: no pair is too large.
+//   chunks   for each 64 entries in order, deferred_waves_chunk (wave =
+//            stencil parameter group) into the pair's cpart rows.
+//   block    thread e sums the rows' value e, which it wrote itself, in chunk
+//            order (pair_block_sum) into pair_blk; a pair without deferred
+//            samples gets pair_reduce_kernel's zeros.
+// The pair's constants and the palette are read once per workgroup.  Barriers
+// only: no atomics, nothing between workgroups, and every value from the
+// operation sequence the five kernels use, so the outputs are theirs bit for
+// bit.  pair_cnt is not written: nothing outside the five-kernel route reads
+// it (pair_block_value reads it in pair_reduce_kernel and in the step
+// epilogue, neither of which runs on this route), and the pair prep clears it
+// every step.  sred / scnt alternate between two slots per tile: a slot is
+// rewritten two barriers after it was read.
+template <int M, bool WS, bool LP, int COARSE>
+__global__ __launch_bounds__(256) void semantic_pair_kernel(SemArgs ak, const uint32_t* __restrict__ mlist,
+                                                            const PairConst* __restrict__ pcs,
+                                                            const uint32_t* __restrict__ pair_tile0,
+                                                            const uint32_t* __restrict__ pair_chunk0,
+                                                            double* __restrict__ cost_partial, uint32_t* dlist,
+                                                            double* cpart, double* __restrict__ pair_blk, int cap_arg) {
+  static_assert(kBlock == 256, "a tile is the workgroup's 256 samples");
+  __shared__ double sraw[64 * 12];      // as semantic_deferred_waves_kernel
+  __shared__ double ssc[64], srs[64];
+  __shared__ double sJ[64 * kSemRow];
+  __shared__ uint8_t sredo[4 * 64];
+  __shared__ double sred[2][kBlock / 64];
+  __shared__ uint32_t scnt[2][kBlock / 64];
+  __shared__ float spal[LP ? 256 : 1];
+  __shared__ uint32_t slist[kSemPairListCap];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint32_t cap = (uint32_t)min(max(cap_arg, 0), kSemPairListCap);
+  const uint32_t p = mlist[blockIdx.x];
+  const SemPair pr = ak.pairs[p];
+  const PairConst* __restrict__ P = pcs + p;
+  const uint32_t tile0 = pair_tile0[p];
+  uint32_t cnt = 0;  // the pair's deferred samples so far (workgroup-uniform)
+  {
+    const SemArgs a = with_pair(ak, P);
+    const float2* dl2 = a.dl + P->roff;
+    const double* K2 = P->K2;
+    if constexpr (LP) {
+      spal[tid] = a.pal[tid];
+      __syncthreads();
+    }
+    const uint32_t ntile = (pr.count + kBlock - 1) / kBlock;
+    SemSample nxt = {{0.0, 0.0, 0.0}, 0.f, 0u};
+    if ((uint32_t)tid < pr.count) nxt = a.samples[(int64_t)pr.start + tid];
+    for (uint32_t j = 0; j < ntile; ++j) {
+      const uint32_t off = j * kBlock + tid;  // the sample's offset in its pair
+      const SemSample smp = nxt;
+      if (off + kBlock < pr.count) nxt = a.samples[(int64_t)pr.start + off + kBlock];
+      double cost = 0.0;
+      bool deferred = false;
+      if (off < pr.count) {
+        Centre c;
+        bool decided;
+        cost = flat_sample<M, WS, LP, COARSE>(a, P, K2, dl2, spal, smp, c, deferred, decided);
+      }
+      const unsigned long long bal = __ballot(deferred);
+      if (lane == 0) scnt[j & 1][wv] = (uint32_t)__popcll(bal);
+      tile_cost_sum(cost, sred[j & 1], tid, lane, cost_partial + tile0 + j);
+      // behind its barrier: the waves' counts
+      const uint32_t c0 = scnt[j & 1][0], c1 = scnt[j & 1][1], c2 = scnt[j & 1][2], c3 = scnt[j & 1][3];
+      if (deferred) {
+        const uint32_t o = cnt + (wv > 0 ? c0 : 0u) + (wv > 1 ? c1 : 0u) + (wv > 2 ? c2 : 0u) +
+                           (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        if (o < cap)
+          slist[o] = off;
+        else
+          dlist[pr.start + o] = off;  // o < the pair's count: inside its region
+      }
+      cnt += ((c0 + c1) + c2) + c3;
+    }
+  }
+  __syncthreads();  // the list is complete (LDS and the pair's dlist region)
+  const uint32_t nch = (cnt + 63) / 64;
+  for (uint32_t c = 0; c < nch; ++c) {
+    const uint32_t k = 64 * c + lane;
+    int64_t n = 0;
+    SemSample smp = {{0.0, 0.0, 0.0}, 0.f, 0u};
+    if (k < cnt) {
+      n = (int64_t)pr.start + (k < cap ? slist[k] : dlist[pr.start + k]);
+      smp = ak.samples[n];
+    }
+    deferred_waves_chunk<M>(ak, pcs, pair_chunk0, cpart, nullptr, 0, nullptr, sraw, ssc, srs, sJ, sredo, tid, lane, wv,
+                            make_uint2(p, 64 * c), cnt, n, smp);
+  }
+  // thread e wrote value e of every row above
+  if (tid < kPairVals)
+    pair_blk[(size_t)p * kPairStride + tid] =
+        pair_block_sum(cpart + (size_t)pair_chunk0[p] * kPairVals + tid, nch, kPairVals);
 }
 
 // The deferred pass's work list: the static list of every pair's possible
@@ -2756,6 +2887,8 @@ mi_ba_status semantic_create(mi_ba_context* ctx, const mi_ba_semantic* sem) {
     S->order_compact = S->npairs > 0;
     for (int m = 0; m < kNumModels; ++m) {
       const uint32_t begin = (uint32_t)mlist.size();
+      S->model_pair0[m] = (int)begin;
+      S->model_pair0[m + 1] = (int)(begin + per[m].size());
       if (per[m].size() > (size_t)kOrderCompactMaxPairs) S->order_compact = false;
       for (size_t r = 0; r < per[m].size(); ++r) {
         const uint32_t last = r + 1 == per[m].size() ? 0x80000000u : 0u;
@@ -2862,6 +2995,11 @@ mi_ba_status semantic_create(mi_ba_context* ctx, const mi_ba_semantic* sem) {
             nb <= 0)
           nb = 4;
         S->dwaves_blocks[1][model] = nb;  // the pipelined loop ("semantic_deferred_pipeline")
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, semantic_pair_kernel<M, false, true, 2>, 256, 0) !=
+                hipSuccess ||
+            nb <= 0)
+          nb = 4;
+        S->pair_blocks[model] = nb;  // "semantic_pair_fused"
       });
     }
   }
@@ -3104,7 +3242,57 @@ mi_ba_status semantic_linearize(mi_ba_context* ctx, double* d_cost, bool write_s
     if (st != MI_BA_OK) return st;
   }
   const bool split = deferred_stream != nullptr && ctx->sem_variant == 6;
-  if (ctx->sem_variant == 6) {
+  // "semantic_pair_fused" 1: one launch of semantic_pair_kernel per model in
+  // place of the flat pass, the ordering and compaction kernels, the four-wave
+  // deferred pass and the pair sums.  Only the product's route: variant 6 with
+  // the four-wave deferred kernel and the default box ("semantic_flat_coarse"
+  // 2, the one form instantiated), no samples to write, no side stream, no
+  // diagnostic.  One workgroup per pair leaves the chip idle when the pairs
+  // are few, so the route is taken only when they fill a resident grid at
+  // least once: pairs >= CUs x the resident workgroups per CU of the
+  // occupancy query (the smallest over the models present; 1024 at four per
+  // CU), or "semantic_pair_min_pairs" when set.  Everything else, every
+  // evaluation that writes samples included, takes the five-kernel route.
+  bool fused = ctx->sem_pair_fused != 0 && ctx->sem_variant == 6 && ctx->sem_dwaves == 4 && !ctx->sem_deferred_box &&
+               ctx->sem_coarse == 2 && !write_samples && !deferred_stream && !after_flat && ctx->sem_diag == 0;
+#ifdef MI_BA_AB_VARIANTS
+  fused = fused && ctx->sem_dvar == 0;
+#endif
+  if (fused) {
+    int min_pairs = ctx->sem_pair_min;
+    if (min_pairs < 0) {
+      int per_cu = 0;
+      for (int model = 0; model < kNumModels; ++model)
+        if (S->model_pair0[model + 1] > S->model_pair0[model])
+          per_cu = per_cu ? std::min(per_cu, S->pair_blocks[model]) : S->pair_blocks[model];
+      min_pairs = std::max(1, per_cu) * S->n_cu;
+    }
+    fused = S->npairs >= min_pairs;
+  }
+  if (fused) {
+    // with timing on, the route shows as launches of "semantic_pair_fused"
+    // (counted, not timed: the time is in "semantic_jacobian")
+    if (ctx->timing) ctx->timer.totals["semantic_pair_fused"].second += 1;
+    const int cap = std::min(ctx->sem_pair_cap, kSemPairListCap);
+    for (int model = 0; model < kNumModels; ++model) {
+      const int p0 = S->model_pair0[model], np = S->model_pair0[model + 1] - p0;
+      if (np == 0) continue;
+      dispatch_model(model, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        auto launch = [&](auto ws_, auto lp_) {
+          hipLaunchKernelGGL((semantic_pair_kernel<M, decltype(ws_)::value, decltype(lp_)::value, 2>), dim3(np),
+                             dim3(256), 0, s, a, S->model_pairs.ptr + p0, pcs, S->pair_tile0.ptr, S->pair_chunk0.ptr,
+                             S->partial.ptr, S->dlist.ptr, S->cpart.ptr, S->pair_blk.ptr, cap);
+        };
+        if (a.lab8)
+          launch(std::false_type{}, std::true_type{});
+        else if (a.wsum)
+          launch(std::true_type{}, std::false_type{});
+        else
+          launch(std::false_type{}, std::false_type{});
+      });
+    }
+  } else if (ctx->sem_variant == 6) {
     const int ws = write_samples ? 1 | (ctx->sem_diag ? 2 : 0) | (ctx->sem_diag == 2 ? 4 : 0) : 0;
     // "semantic_deferred_pipeline": the four-wave kernel's resident loop reads
     // ahead; the list kernels write each chunk's pair count and start (dext)
@@ -3278,7 +3466,7 @@ mi_ba_status semantic_linearize(mi_ba_context* ctx, double* d_cost, bool write_s
     });
   }
 #endif
-  if (epilogue) {
+  if (epilogue && !fused) {
     // the timer still ends behind the finished pair blocks (it now holds the cost sums too)
     launch_sum2_pairs(other_partial, other_n, other_out, other_scratch, S->partial.ptr, S->ntiles, d_cost,
                       PairBlocks{S->pair_cnt.ptr, S->pair_chunk0.ptr, S->cpart.ptr, S->pair_blk.ptr, S->npairs, kPairVals,

@@ -87,15 +87,20 @@ __device__ inline void touch_ranges(const TouchRanges& t, unsigned* sink, int bl
 // Value e of pair p's block from the deferred pass's chunk partials, summed
 // in chunk order (the body of pair_reduce_kernel; a pair without deferred
 // samples gets zeros: its cleared samples have J = 0).
+// pair_block_sum: the sum itself over the pair's nch chunk rows, the first at c
+// (semantic_pair_kernel sums the rows its own workgroup wrote: no restrict).
+__device__ inline double pair_block_sum(const double* c, uint32_t nch, int vals) {
+  double v = 0.0;
+  for (uint32_t j = 0; j < nch; ++j) v += c[(size_t)j * vals];
+  return v;
+}
+
 __device__ inline void pair_block_value(const uint32_t* __restrict__ pair_cnt,
                                         const uint32_t* __restrict__ pair_chunk0, const double* __restrict__ cpart,
                                         double* __restrict__ pair_blk, int vals, int blk_stride, int p, int e) {
   if (e >= vals) return;
   const uint32_t nch = (pair_cnt[p] + 63) / 64;
-  const double* c = cpart + (size_t)pair_chunk0[p] * vals + e;
-  double v = 0.0;
-  for (uint32_t j = 0; j < nch; ++j) v += c[(size_t)j * vals];
-  pair_blk[(size_t)p * blk_stride + e] = v;
+  pair_blk[(size_t)p * blk_stride + e] = pair_block_sum(cpart + (size_t)pair_chunk0[p] * vals + e, nch, vals);
 }
 
 }  // namespace miba
