@@ -635,6 +635,136 @@ mi_ba_status mi_ba_dense_cholesky(int32_t device, int32_t n, double* A, double* 
 mi_ba_status mi_ba_dense_cholesky_ex(int32_t device, int32_t n, double* A, double* b, int32_t panel,
                                      int32_t lookahead, int32_t own_diag, int32_t solve, int32_t* info);
 
+/* --- camera rigs -----------------------------------------------------------
+ * Additive entry points: no existing struct or function changes, so
+ * MI_BA_ABI_VERSION stays 4 (the suite pins that number).
+ * RigBundleAdjuster (src/optim/bundle_adjustment.h:270-327,
+ * bundle_adjustment.cc:789-1140) with CameraRig (src/base/camera_rig.{h,cc}).
+ * A rig image's pose is ConcatenatePoses(rig pose of its snapshot, relative
+ * pose of its camera): q = q_rel * q_rig, t = R(q_rel) t_rig + t_rel
+ * (RigBundleAdjustmentCostFunction, src/base/cost_functions.h:160-214).
+ *
+ * mi_ba_rig: num_rigs rigs; rig r owns the cameras rig_camera[rig_camera_off[r]
+ * .. rig_camera_off[r + 1]) (problem camera indices) with their relative poses
+ * rel_qvec / rel_tvec in the same positions, its reference camera
+ * rig_ref_camera[r] (a problem camera index; -1 = CameraRig's kInvalidCameraId)
+ * and the snapshots rig_snapshot_off[r] .. rig_snapshot_off[r + 1); snapshot s
+ * holds the images snapshot_image[snapshot_off[s] .. snapshot_off[s + 1])
+ * (problem image indices) and has the absolute rig pose snapshot_qvec[s],
+ * snapshot_tvec[s]. */
+typedef struct mi_ba_rig {
+  int32_t num_rigs;
+  const int32_t* rig_camera_off;     /* [num_rigs + 1] */
+  const int32_t* rig_camera;         /* [rig_camera_off[num_rigs]] */
+  const int32_t* rig_ref_camera;     /* [num_rigs] */
+  double* rel_qvec;                  /* (in/out) [rig_camera_off[num_rigs]][4] */
+  double* rel_tvec;                  /* (in/out) [rig_camera_off[num_rigs]][3] */
+  const int32_t* rig_snapshot_off;   /* [num_rigs + 1] */
+  int32_t num_snapshots;             /* = rig_snapshot_off[num_rigs] */
+  const int32_t* snapshot_off;       /* [num_snapshots + 1] */
+  const int32_t* snapshot_image;     /* [snapshot_off[num_snapshots]] */
+  double* snapshot_qvec;             /* (in/out) [num_snapshots][4] */
+  double* snapshot_tvec;             /* (in/out) [num_snapshots][3] */
+  int32_t refine_relative_poses;     /* RigBundleAdjuster::Options, default 1 */
+  double max_reproj_error;           /* RigBundleAdjuster::Options, default 1000 */
+} mi_ba_rig;
+
+void mi_ba_default_rig(mi_ba_rig* rig);
+
+/* Reduced-program counts of the rig problem (RigBundleAdjuster::SetUp +
+ * Ceres' reduced-program rule; no device needed).  num_variable_images counts
+ * the variable poses of images in no rig; the snapshot rig poses and relative
+ * poses that are variable and carry an observation are counted in
+ * num_effective_parameters_reduced (6 each).  Rig images' observations are
+ * filtered by max_reproj_error at the concatenated pose (:970-975).
+ * MI_BA_ERR_INVALID_ARGUMENT where the reference CHECKs (Solve :800-817,
+ * AddImageToProblem :927-930, CameraRig::Check): a camera in two rigs (or
+ * twice in one), an image in two snapshots or two rigs, a snapshot image whose
+ * camera is not in the rig, two images of one snapshot with the same camera, a
+ * rig image with a constant pose or a constant tvec, a rig without a
+ * reference camera of its own or a snapshot without an image of it, an empty
+ * snapshot, a snapshot with more images than the rig has cameras. */
+mi_ba_status mi_ba_rig_setup_stats(const mi_ba_options* options, const mi_ba_problem* problem,
+                                   const mi_ba_rig* rig, mi_ba_setup_info* info);
+
+/* RigBundleAdjuster::Solve on the GPU.  The LM runs over the rig parameters:
+ * per iteration the undamped reduced camera system of the per-image problem is
+ * projected onto them (S_rig = T^T S T, b_rig = T^T b, T below), damped and
+ * factored there, and the step is expanded back (d_img = T d_rig) for the back
+ * substitution; candidates are the concatenation of the candidate rig poses.
+ * On return (unless the solve ends in MI_BA_FAILURE / MI_BA_USER_FAILURE):
+ * the variable rig poses and relative poses, the cameras and the points are
+ * written back, and every snapshot image's qvec / tvec is ConcatenatePoses of
+ * the returned poses (TearDown, bundle_adjustment.cc:891-903).  The relative
+ * pose of a reference camera, and every relative pose without
+ * refine_relative_poses, is left bit for bit as given.
+ * Rig problems take the exact reduced-camera path: MI_BA_SOLVER_ITERATIVE_SCHUR
+ * returns MI_BA_ERR_UNSUPPORTED (as do a semantic term, a communicator and a
+ * host reducer on a rig context, below; the GSBA term has no rig entry
+ * point). */
+mi_ba_status mi_ba_rig_solve(const mi_ba_options* options, mi_ba_problem* problem, mi_ba_rig* rig,
+                             mi_ba_summary* summary);
+
+/* A resident rig context: as mi_ba_context_create with the rigs, for
+ * mi_ba_context_solve / mi_ba_context_writeback (which also writes the rig
+ * arrays, as mi_ba_rig_solve), the timing entries ("rig_project", "cholesky",
+ * "schur_build", ...) and mi_ba_set_tuning.  The rig struct's arrays must
+ * outlive the context.  Combinations that are follow-ups return
+ * MI_BA_ERR_UNSUPPORTED instead of a wrong solve: a semantic term (here), and
+ * mi_ba_context_set_comm / mi_ba_context_set_host_reducer on a rig context. */
+mi_ba_status mi_ba_rig_context_create(const mi_ba_options* options, const mi_ba_problem* problem,
+                                      const mi_ba_semantic* semantic /* must be NULL */, const mi_ba_rig* rig,
+                                      mi_ba_context** ctx);
+
+/* Parity download of the rig Jacobian at the given parameters.  Per reduced
+ * block (the library's point-major order; block_obs[k] = the problem
+ * observation of block k): residuals [n][2] and jacobians [n][2][15 + c],
+ * columns rig pose (rot 3, trans 3), relative pose (6), point (3), refined
+ * intrinsics (c = camera_tangent_size), corrected by the loss as
+ * mi_ba_download_jacobian's.  Columns of constant blocks are zero; a block of
+ * an image in no rig carries the image pose in the first six columns and zeros
+ * in the second six.  The per-image Jacobian comes from the reprojection
+ * kernel, the maps A_i, B_i from the device records the solver's projection
+ * uses.  *num_blocks receives the count; nothing else is written when it
+ * exceeds capacity. */
+mi_ba_status mi_ba_rig_evaluate(const mi_ba_options* options, const mi_ba_problem* problem, const mi_ba_rig* rig,
+                                int64_t capacity, int64_t* num_blocks, int64_t* block_obs, double* residuals,
+                                double* jacobians);
+
+/* The rig tangent map T.  With Ceres' QuaternionManifold the tangent of rig
+ * image i is linear in the tangents of its owners: d_img(i) = A_i d_owner(i)
+ * + B_i d_rel(i).  Per-image layout: 6 per image (rotation 3, translation 3),
+ * then num_intrinsics columns.  Rig layout: 6 per slot, then the same
+ * num_intrinsics columns (T is the identity there).  owner_slot[i] in
+ * [0, num_slots) with the 6 x 6 row-major A_i (the identity for an image in no
+ * rig), or -1 for an image without a variable pose (its rows of T are zero);
+ * rel_slot[i] in [0, num_slots) with B_i, or -1 (B_i not read). */
+typedef struct mi_ba_rig_table {
+  int32_t num_images;
+  int32_t num_intrinsics;
+  int32_t num_slots;
+  const int32_t* owner_slot;         /* [num_images] */
+  const int32_t* rel_slot;           /* [num_images], -1 = none */
+  const double* A;                   /* [num_images][36] */
+  const double* B;                   /* [num_images][36] */
+} mi_ba_rig_table;
+
+/* The projection kernel alone, on host buffers in and out (as
+ * mi_ba_dense_cholesky exposes the factorisation): S_rig = T^T S_img T and
+ * b_rig = T^T b_img.  S_img: row-major n_img x n_img, n_img = 6 num_images +
+ * num_intrinsics; only its upper triangle (column >= row) is read.  S_rig:
+ * row-major n_rig x n_rig, n_rig = 6 num_slots + num_intrinsics; its upper
+ * triangle is written, the strict lower triangle is set to zero.  b_img /
+ * b_rig: nullable together.  Every sum runs in a fixed order (no
+ * floating-point atomics): two calls give the same bits.  An output block
+ * whose owners have more than mi_ba_rig_project_chunk() member pairs is summed
+ * in chunks of that many and combined in chunk order. */
+mi_ba_status mi_ba_rig_reduce_dense(int32_t device, int32_t n_img, const double* S_img, const double* b_img,
+                                    const mi_ba_rig_table* table, int32_t n_rig, double* S_rig, double* b_rig);
+/* Member pairs per chunk of the projection kernel; *lanes (nullable) = member
+ * pairs of one pass of its member loop. */
+int32_t mi_ba_rig_project_chunk(int32_t* lanes);
+
 /* Per-kernel HIP-event timing on the context's stream (enabled with
  * mi_ba_set_timing).  name: "reproj_jacobian", "semantic_jacobian", ... */
 mi_ba_status mi_ba_set_timing(mi_ba_context* ctx, int32_t enabled);

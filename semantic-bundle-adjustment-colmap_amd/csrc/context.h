@@ -52,6 +52,7 @@ struct DevArray {
 
 struct SemanticState;  // semantic.h
 struct GsbaState;      // gsba.h
+struct RigState;       // rig.h
 
 struct KernelTimer {
   std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
@@ -208,6 +209,7 @@ struct mi_ba_context {
   double fixed_cost = 0.0;
   miba::SemanticState* sem = nullptr;
   miba::GsbaState* gsba = nullptr;        // geometric-semantic (cylinder IoU) term
+  miba::RigState* rig = nullptr;          // camera rigs: the reduced camera system projected onto the rig parameters
 
   bool timing = false;
   miba::KernelTimer timer;
@@ -240,7 +242,8 @@ mi_ba_status context_create(const mi_ba_options* o, const mi_ba_problem* p, cons
 // device arrays (re-sized in place when large enough) carry over, the problem
 // state is replaced.  On failure `old` is destroyed and *out is null.
 mi_ba_status context_recycle(mi_ba_context* old, const mi_ba_options* o, const mi_ba_problem* p,
-                             const mi_ba_semantic* sem, mi_ba_context** out, const mi_ba_gsba* gsba = nullptr);
+                             const mi_ba_semantic* sem, mi_ba_context** out, const mi_ba_gsba* gsba = nullptr,
+                             const mi_ba_rig* rig = nullptr);
 void context_destroy(mi_ba_context* ctx);
 mi_ba_status context_linearize(mi_ba_context* ctx, double* cost_out);
 mi_ba_status context_solve(mi_ba_context* ctx, mi_ba_summary* sum);

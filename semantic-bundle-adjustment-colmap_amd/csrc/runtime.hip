@@ -33,6 +33,7 @@
 #include "context.h"
 #include "kernels.h"
 #include "gsba.h"
+#include "rig.h"
 #include "semantic.h"
 #include "setup.h"
 #include <rocsolver/rocsolver.h>
@@ -621,6 +622,7 @@ namespace {
 void reset_problem_state(mi_ba_context* ctx) {
   semantic_destroy(ctx);
   gsba_destroy(ctx);
+  rig_destroy(ctx);
   ctx->timer.totals.clear();
   ctx->timing = false;
   ctx->solved = false;
@@ -635,7 +637,8 @@ void reset_problem_state(mi_ba_context* ctx) {
 }  // namespace
 
 mi_ba_status context_recycle(mi_ba_context* old, const mi_ba_options* o, const mi_ba_problem* pin,
-                             const mi_ba_semantic* sem, mi_ba_context** out, const mi_ba_gsba* gsba) {
+                             const mi_ba_semantic* sem, mi_ba_context** out, const mi_ba_gsba* gsba,
+                             const mi_ba_rig* rig) {
   if (!o || !pin || !out) {
     context_destroy(old);
     return MI_BA_ERR_INVALID_ARGUMENT;
@@ -668,7 +671,11 @@ mi_ba_status context_recycle(mi_ba_context* old, const mi_ba_options* o, const m
   ctx->device = o->device;
   auto fail = [&](mi_ba_status e) { context_destroy(ctx); return e; };
   mi_ba_problem* p = &ctx->problem;
-  mi_ba_status st = build_setup(*o, p, &ctx->setup);
+  // Rig problems always take the exact reduced-camera path; the PCG path and
+  // rigs beside the semantic / GSBA terms are follow-ups (refused, not mis-solved)
+  if (rig && (o->linear_solver_type == MI_BA_SOLVER_ITERATIVE_SCHUR || sem || gsba)) return fail(MI_BA_ERR_UNSUPPORTED);
+  RigSetup rig_setup;
+  mi_ba_status st = rig ? build_rig_setup(*o, p, *rig, &ctx->setup, &rig_setup) : build_setup(*o, p, &ctx->setup);
   if (st != MI_BA_OK) return fail(st);
   const HostSetup& s = ctx->setup;
   if (!ctx->stream && hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -940,6 +947,10 @@ mi_ba_status context_recycle(mi_ba_context* old, const mi_ba_options* o, const m
     } else if (o->linear_solver_type == MI_BA_SOLVER_AUTO) {
       ctx->dense = ncfg <= 1000 && fits;
     }
+    if (rig) {
+      if (!fits) return fail(MI_BA_ERR_UNSUPPORTED);
+      ctx->dense = true;
+    }
     if (ctx->dense) {
       // S's leading dimension: one spare column-major row (the rhs carried
       // through the factorisation), rounded to 16 doubles (128-B columns)
@@ -994,6 +1005,10 @@ mi_ba_status context_recycle(mi_ba_context* old, const mi_ba_options* o, const m
     st = gsba_create(ctx, gsba);
     if (st != MI_BA_OK) return fail(st);
   }
+  if (rig) {
+    st = rig_create(ctx, *rig, std::move(rig_setup));
+    if (st != MI_BA_OK) return fail(st);
+  }
   *out = ctx;
   return MI_BA_OK;
 }
@@ -1008,6 +1023,7 @@ void context_destroy(mi_ba_context* ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   semantic_destroy(ctx);
   gsba_destroy(ctx);
+  rig_destroy(ctx);
   for (auto& e : ctx->timer.pending) {
     (void)hipEventDestroy(e.second.first);
     (void)hipEventDestroy(e.second.second);
@@ -1394,8 +1410,13 @@ mi_ba_status gradient_reached(mi_ba_context* ctx, bool* reached) {
   if (ctx->gsba) gsba_add_gradient(ctx, g);
   st = allreduce(ctx, g, d.nf);
   if (st != MI_BA_OK) return st;
-  launch_grad_max_f(d, g, aux + nw, s);
+  {
+    DevProblem dn = d;
+    if (ctx->rig) dn.img_flags = ctx->rig->flags_free.ptr;
+    launch_grad_max_f(dn, g, aux + nw, s);
+  }
   if (ctx->gsba) gsba_grad_max(ctx, g, aux + nw);
+  if (ctx->rig) rig_grad_max(ctx, g, aux + nw);  // g_rig = T' g
   MI_HIP(hipMemcpyAsync(h.data() + nw, aux + nw, 8, hipMemcpyDeviceToHost, s));
   MI_HIP_DRAIN(ctx, s);
   gmax = std::max(gmax, h[nw]);
@@ -1474,7 +1495,7 @@ mi_ba_status chol_check_pending(mi_ba_context* ctx, bool* ok) {
 mi_ba_status dense_solve(mi_ba_context* ctx, bool* ok, bool schur_launched) {
   const DevProblem& d = ctx->dev;
   hipStream_t s = ctx->stream;
-  const int64_t nf = d.nf;
+  const int64_t nf = ctx->rig ? ctx->rig->nf : d.nf;
   *ok = true;
   hipEvent_t stop;
   // S was zeroed and took U from launch_fblock_dense (context_solve)
@@ -1497,21 +1518,35 @@ mi_ba_status dense_solve(mi_ba_context* ctx, bool* ok, bool schur_launched) {
       if (st != MI_BA_OK) return st;
     }
   }
-  timer_begin(ctx, "schur_build", &stop);
-  launch_dense_finalize(d, ctx->lambda_f.ptr, ctx->S.ptr, s);
-  timer_end(ctx, stop);
+  // Rigs: the undamped S and the rhs are projected onto the rig parameters
+  // (S_rig = T' S T, b_rig = T' b), damped there, and the factorisation and
+  // the sweeps below run on S_rig; the step is expanded to cg_x = T x_rig.
+  double* const Sp = ctx->rig ? ctx->rig->S.ptr : ctx->S.ptr;
+  double* const bp = ctx->rig ? ctx->rig->b.ptr : ctx->bvec.ptr;
+  double* const xp = ctx->rig ? ctx->rig->x.ptr : ctx->cg_x.ptr;
+  const int64_t lds = ctx->rig ? ctx->rig->lds : d.lds;
+  if (ctx->rig) {
+    timer_begin(ctx, "rig_project", &stop);
+    const mi_ba_status rst = rig_project(ctx);
+    timer_end(ctx, stop);
+    if (rst != MI_BA_OK) return rst;
+  } else {
+    timer_begin(ctx, "schur_build", &stop);
+    launch_dense_finalize(d, ctx->lambda_f.ptr, ctx->S.ptr, s);
+    timer_end(ctx, stop);
+  }
   // fused: the rhs rides in S's spare row and leaves it as the forward
   // solution y = L^-1 b (one backward sweep left); else the two sweeps on b
   const bool fused = fused_rhs(ctx);
   const unsigned gn = (unsigned)((nf + 255) / 256);
   if (fused)
-    hipLaunchKernelGGL(rhs_row_kernel, dim3(gn), dim3(256), 0, s, ctx->S.ptr, nf, d.lds, ctx->bvec.ptr, 1);
+    hipLaunchKernelGGL(rhs_row_kernel, dim3(gn), dim3(256), 0, s, Sp, nf, lds, bp, 1);
   else
-    MI_HIP(hipMemcpyAsync(ctx->cg_x.ptr, ctx->bvec.ptr, nf * 8, hipMemcpyDeviceToDevice, s));
+    MI_HIP(hipMemcpyAsync(xp, bp, nf * 8, hipMemcpyDeviceToDevice, s));
   timer_begin(ctx, "cholesky", &stop);
   // S holds the upper triangle row-major == the lower triangle column-major.
   const int leaves = chol_leaf_count((int)nf, ctx->chol);
-  if (chol_factor(ctx->blas, (int)nf, ctx->S.ptr, (int)d.lds, ctx->info.ptr, ctx->chol, &ctx->cholws,
+  if (chol_factor(ctx->blas, (int)nf, Sp, (int)lds, ctx->info.ptr, ctx->chol, &ctx->cholws,
                   fused ? 1 : 0) != rocblas_status_success)
     return MI_BA_ERR_HIP;
   timer_end(ctx, stop);
@@ -1532,14 +1567,14 @@ mi_ba_status dense_solve(mi_ba_context* ctx, bool* ok, bool schur_launched) {
   {
     Phase ph_(ctx, "cholesky_solve");
     if (fused) {
-      hipLaunchKernelGGL(rhs_row_kernel, dim3(gn), dim3(256), 0, s, ctx->S.ptr, nf, d.lds, ctx->cg_x.ptr, 0);
-      if (chol_solve_backward(ctx->blas, (int)nf, ctx->S.ptr, (int)d.lds, ctx->cg_x.ptr, &ctx->cholws) !=
-          rocblas_status_success)
+      hipLaunchKernelGGL(rhs_row_kernel, dim3(gn), dim3(256), 0, s, Sp, nf, lds, xp, 0);
+      if (chol_solve_backward(ctx->blas, (int)nf, Sp, (int)lds, xp, &ctx->cholws) != rocblas_status_success)
         return MI_BA_ERR_HIP;
-    } else if (chol_solve(ctx->blas, (int)nf, ctx->S.ptr, (int)d.lds, ctx->cg_x.ptr, ctx->chol.solve, &ctx->cholws) !=
+    } else if (chol_solve(ctx->blas, (int)nf, Sp, (int)lds, xp, ctx->chol.solve, &ctx->cholws) !=
                rocblas_status_success) {
       return MI_BA_ERR_HIP;
     }
+    if (ctx->rig) rig_expand(ctx);
   }
   if (ctx->fail_factorizations > 0) {  // test hook
     --ctx->fail_factorizations;
@@ -1597,6 +1632,7 @@ mi_ba_status run_callbacks(mi_ba_context* ctx, const mi_ba_iteration_summary& it
 
 mi_ba_status context_solve(mi_ba_context* ctx, mi_ba_summary* sum) {
   if (ctx->solved) return MI_BA_ERR_STATE;
+  if (ctx->rig && ctx->distributed()) return MI_BA_ERR_UNSUPPORTED;  // multi-rank rigs: a follow-up
   ctx->solved = true;
   ctx->chol_pending = false;
   const double t_start = now_s();
@@ -1687,7 +1723,7 @@ mi_ba_status context_solve(mi_ba_context* ctx, mi_ba_summary* sum) {
     // flushes (det_sums) update S's diagonal blocks by plain read-modify-write
     // in FlushDense and in the Schur pair / owner flushes, which must not run
     // concurrently
-    const bool schur_side = ctx->dense && !ctx->distributed() && ctx->schur_overlap && !ctx->det_sums;
+    const bool schur_side = ctx->dense && !ctx->distributed() && ctx->schur_overlap && !ctx->det_sums && !ctx->rig;
     if (schur_side) {
       if (!ctx->lm_side) {
         if (hipStreamCreateWithFlags(&ctx->lm_side, hipStreamNonBlocking) != hipSuccess) {
@@ -1715,6 +1751,8 @@ mi_ba_status context_solve(mi_ba_context* ctx, mi_ba_summary* sum) {
                       ctx->udiag.ptr, s, ctx->owners());
       if (ctx->sem) semantic_add_fblock(ctx);
       if (ctx->gsba) gsba_add_fblock(ctx);
+      // S holds U alone here: the rig parameters' diagonal, scaling and damping
+      if (ctx->rig) rig_udiag(ctx, first, reuse_diag, radius);
     }
     if (ctx->distributed()) {
       Phase ph_(ctx, "f_allreduce");
@@ -1802,6 +1840,7 @@ mi_ba_status context_solve(mi_ba_context* ctx, mi_ba_summary* sum) {
     launch_plus(d, ctx->cg_x.ptr, ctx->dX.ptr, ctx->qt.ptr, ctx->cam.ptr, ctx->X.ptr, ctx->qt_c.ptr,
                 ctx->cam_c.ptr, ctx->X_c.ptr, s);
     if (ctx->gsba) gsba_plus(ctx, ctx->cg_x.ptr);
+    if (ctx->rig) rig_plus(ctx, ctx->qt_c.ptr);  // the rig images' candidates: concatenated candidate rig poses
     MI_HIP(hipMemsetAsync(sc + kCandCost, 0, 8, s));
     MI_HIP(hipMemsetAsync(sc + kSemCand, 0, 8, s));
     MI_HIP(hipMemsetAsync(sc + kGsCand, 0, 8, s));
@@ -1815,8 +1854,14 @@ mi_ba_status context_solve(mi_ba_context* ctx, mi_ba_summary* sum) {
     // Ceres' |x|^2 and |x - candidate_x|^2 over the variable blocks, ambient
     // coordinates (kXB, kXR: PCG scratch, free here); images, cameras and
     // cylinders counted on rank 0, points on their own ranks
-    launch_state_norms(d, ctx->qt_c.ptr, ctx->cam_c.ptr, ctx->X_c.ptr, ctx->rank == 0, sc + kXB, ctx->red.ptr, s);
+    {
+      // rigs: the rig images' poses are no parameter blocks; the rig's are
+      DevProblem dn = d;
+      if (ctx->rig) dn.img_flags = ctx->rig->flags_free.ptr;
+      launch_state_norms(dn, ctx->qt_c.ptr, ctx->cam_c.ptr, ctx->X_c.ptr, ctx->rank == 0, sc + kXB, ctx->red.ptr, s);
+    }
     if (ctx->gsba && ctx->rank == 0) gsba_state_norms(ctx, sc + kXB);
+    if (ctx->rig) rig_state_norms(ctx, sc + kXB);
     if (ctx->distributed()) {
       st = allreduce(ctx, sc + kCandCost, 1);
       if (st == MI_BA_OK) st = allreduce(ctx, sc + kSemCand, 1);
@@ -1856,6 +1901,7 @@ mi_ba_status context_solve(mi_ba_context* ctx, mi_ba_summary* sum) {
       ctx->dev.cam = ctx->cam.ptr;
       ctx->dev.X = ctx->X.ptr;
       if (ctx->gsba) gsba_accept(ctx);
+      if (ctx->rig) rig_accept(ctx);
       radius = radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * relative_decrease - 1.0, 3));
       radius = std::min(1e16, radius);
       decrease_factor = 2.0;
@@ -1901,6 +1947,7 @@ mi_ba_status context_writeback(mi_ba_context* ctx) {
     if (!s.pt_var[k]) continue;
     for (int m = 0; m < 3; ++m) p->xyz[3 * k + m] = X[3 * k + m];
   }
+  if (ctx->rig) return rig_writeback(ctx);
   if (ctx->gsba) return gsba_writeback(ctx);
   return MI_BA_OK;
 }
@@ -2040,11 +2087,11 @@ bool solution_usable(const mi_ba_summary& s) {
 // One BundleAdjuster::Solve on *arena (recycled, or created when null); the
 // context is kept in *arena for the next solve, or destroyed on failure.
 mi_ba_status solve_on(mi_ba_context** arena, const mi_ba_options* o, mi_ba_problem* p, const mi_ba_semantic* sem,
-                      mi_ba_summary* sum) {
+                      mi_ba_summary* sum, const mi_ba_rig* rig = nullptr) {
   if (!o || !p || !sum) return MI_BA_ERR_INVALID_ARGUMENT;
   const double t0 = now_s();
   mi_ba_context* ctx = nullptr;
-  mi_ba_status st = context_recycle(*arena, o, p, sem, &ctx);
+  mi_ba_status st = context_recycle(*arena, o, p, sem, &ctx, nullptr, rig);
   *arena = ctx;
   if (st != MI_BA_OK) return st;
   // SetUp normalised the config qvecs of ctx->problem (== caller arrays).
@@ -2055,10 +2102,63 @@ mi_ba_status solve_on(mi_ba_context** arena, const mi_ba_options* o, mi_ba_probl
     *arena = nullptr;
   }
   sum->total_time_in_seconds = now_s() - t0;
-  if (st == MI_BA_OK && o->print_summary) print_summary(*sum);
+  if (st == MI_BA_OK && o->print_summary) {
+    if (rig) std::printf("\nRig Bundle adjustment report\n----------------------------\n");
+    print_summary(*sum);
+  }
   return st;
 }
 }  // namespace
+
+mi_ba_status mi_ba_rig_context_create(const mi_ba_options* o, const mi_ba_problem* p, const mi_ba_semantic* sem,
+                                      const mi_ba_rig* rig, mi_ba_context** ctx) {
+  if (!rig) {
+    if (ctx) *ctx = nullptr;
+    return MI_BA_ERR_INVALID_ARGUMENT;
+  }
+  return context_recycle(nullptr, o, p, sem, ctx, nullptr, rig);
+}
+
+mi_ba_status mi_ba_rig_evaluate(const mi_ba_options* o, const mi_ba_problem* p, const mi_ba_rig* rig,
+                                int64_t capacity, int64_t* num_blocks, int64_t* block_obs, double* residuals,
+                                double* jacobians) {
+  if (!o || !p || !rig || !num_blocks) return MI_BA_ERR_INVALID_ARGUMENT;
+  // SetUp normalises qvecs in place; work on a private copy of the qvecs.
+  mi_ba_problem copy = *p;
+  std::vector<double> q;
+  if (p->qvec && p->num_images > 0) q.assign(p->qvec, p->qvec + 4 * (size_t)p->num_images);
+  copy.qvec = p->qvec ? q.data() : nullptr;
+  mi_ba_context* ctx = nullptr;
+  mi_ba_status st = context_recycle(nullptr, o, &copy, nullptr, &ctx, nullptr, rig);
+  if (st != MI_BA_OK) return st;
+  const int64_t nb = ctx->dev.nb;
+  *num_blocks = nb;
+  if (nb <= capacity && nb > 0) {
+    st = context_linearize(ctx, nullptr);
+    std::vector<double> J((size_t)nb * 2 * ctx->dev.W);
+    if (st == MI_BA_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = MI_BA_ERR_HIP;
+    if (st == MI_BA_OK && block_obs) std::memcpy(block_obs, ctx->block_obs.data(), nb * sizeof(int64_t));
+    if (st == MI_BA_OK && residuals &&
+        hipMemcpy(residuals, ctx->r.ptr, nb * sizeof(double2), hipMemcpyDeviceToHost) != hipSuccess)
+      st = MI_BA_ERR_HIP;
+    if (st == MI_BA_OK && jacobians) {
+      if (hipMemcpy(J.data(), ctx->J.ptr, J.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        st = MI_BA_ERR_HIP;
+      else
+        st = rig_block_jacobians(ctx, J.data(), jacobians);
+    }
+  }
+  context_destroy(ctx);
+  return st;
+}
+
+mi_ba_status mi_ba_rig_solve(const mi_ba_options* o, mi_ba_problem* p, mi_ba_rig* rig, mi_ba_summary* sum) {
+  if (!rig) return MI_BA_ERR_INVALID_ARGUMENT;
+  mi_ba_context* ctx = nullptr;
+  const mi_ba_status st = solve_on(&ctx, o, p, nullptr, sum, rig);
+  context_destroy(ctx);
+  return st;
+}
 
 void mi_ba_default_gsba(mi_ba_gsba* g) {
   if (!g) return;
@@ -2312,6 +2412,7 @@ int32_t mi_ba_comm_pending_setups(void) { return g_setup_helpers.load(); }
 mi_ba_status mi_ba_context_set_comm(mi_ba_context* ctx, int32_t rank, int32_t world,
                                     const char id[MI_BA_COMM_ID_BYTES]) {
   if (!ctx || !id || world < 1 || rank < 0 || rank >= world) return MI_BA_ERR_INVALID_ARGUMENT;
+  if (ctx->rig) return MI_BA_ERR_UNSUPPORTED;  // multi-rank rigs: a follow-up
   if (ctx->comm || ctx->host_reduce || ctx->solved) return MI_BA_ERR_STATE;
   MI_HIP(hipSetDevice(ctx->device));
   if (ctx->comm_failed) return MI_BA_ERR_STATE;
@@ -2395,6 +2496,7 @@ mi_ba_status mi_ba_context_set_comm(mi_ba_context* ctx, int32_t rank, int32_t wo
 mi_ba_status mi_ba_context_set_host_reducer(mi_ba_context* ctx, int32_t rank, int32_t world,
                                             mi_ba_host_allreduce_fn fn, void* user) {
   if (!ctx || !fn || world < 1 || rank < 0 || rank >= world) return MI_BA_ERR_INVALID_ARGUMENT;
+  if (ctx->rig) return MI_BA_ERR_UNSUPPORTED;  // multi-rank rigs: a follow-up
   if (ctx->comm || ctx->host_reduce || ctx->solved) return MI_BA_ERR_STATE;
   ctx->host_reduce = fn;
   ctx->host_reduce_user = user;

@@ -227,6 +227,37 @@ class SetupInfo(C.Structure):
     ]
 
 
+class Rig(C.Structure):
+    _fields_ = [
+        ("num_rigs", C.c_int32),
+        ("rig_camera_off", _i32p),
+        ("rig_camera", _i32p),
+        ("rig_ref_camera", _i32p),
+        ("rel_qvec", _dp),
+        ("rel_tvec", _dp),
+        ("rig_snapshot_off", _i32p),
+        ("num_snapshots", C.c_int32),
+        ("snapshot_off", _i32p),
+        ("snapshot_image", _i32p),
+        ("snapshot_qvec", _dp),
+        ("snapshot_tvec", _dp),
+        ("refine_relative_poses", C.c_int32),
+        ("max_reproj_error", C.c_double),
+    ]
+
+
+class RigTable(C.Structure):
+    _fields_ = [
+        ("num_images", C.c_int32),
+        ("num_intrinsics", C.c_int32),
+        ("num_slots", C.c_int32),
+        ("owner_slot", _i32p),
+        ("rel_slot", _i32p),
+        ("A", _dp),
+        ("B", _dp),
+    ]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [
         ("camera_model", C.c_int32),
@@ -309,6 +340,18 @@ def load(path: str = LIB_PATH):
     lib.mi_ba_filter_points3d.argtypes = [C.c_void_p, C.c_double, _u8p, C.c_int32, _u8p, _u8p, _dp,
                                           C.POINTER(C.c_int64)]
     lib.mi_ba_positive_depth.argtypes = [C.c_void_p, _u8p, C.c_int32, _u8p, C.POINTER(C.c_int64)]
+    lib.mi_ba_default_rig.argtypes = [C.POINTER(Rig)]
+    lib.mi_ba_default_rig.restype = None
+    lib.mi_ba_rig_setup_stats.argtypes = [C.POINTER(Options), C.POINTER(Problem), C.POINTER(Rig),
+                                          C.POINTER(SetupInfo)]
+    lib.mi_ba_rig_solve.argtypes = [C.POINTER(Options), C.POINTER(Problem), C.POINTER(Rig), C.POINTER(Summary)]
+    lib.mi_ba_rig_context_create.argtypes = [C.POINTER(Options), C.POINTER(Problem), C.POINTER(Semantic),
+                                             C.POINTER(Rig), C.POINTER(C.c_void_p)]
+    lib.mi_ba_rig_evaluate.argtypes = [C.POINTER(Options), C.POINTER(Problem), C.POINTER(Rig), C.c_int64, _i64p, _i64p,
+                                       _dp, _dp]
+    lib.mi_ba_rig_reduce_dense.argtypes = [C.c_int32, C.c_int32, _dp, _dp, C.POINTER(RigTable), C.c_int32, _dp, _dp]
+    lib.mi_ba_rig_project_chunk.argtypes = [_i32p]
+    lib.mi_ba_rig_project_chunk.restype = C.c_int32
     _lib = lib
     return lib
 
@@ -532,6 +575,129 @@ def dense_cholesky(A: np.ndarray, b: Optional[np.ndarray] = None, device: int = 
     check(load().mi_ba_dense_cholesky_ex(device, n, F.ctypes.data_as(_dp), _ptr(x, _dp), panel, lookahead, own_diag,
                                          solve, C.byref(info)), "mi_ba_dense_cholesky_ex")
     return np.tril(F), x, info.value
+
+
+@dataclass
+class RigInput:
+    """mi_ba_rig: camera rigs over a Scene.  rigs: one dict per rig with
+    "cameras" (problem camera indices), "ref_camera", "rel_qvec" [k][4],
+    "rel_tvec" [k][3] (one per camera, same order) and "snapshots" (lists of
+    problem image indices); snapshot_qvec / snapshot_tvec: the snapshots'
+    absolute rig poses, rigs back to back."""
+    rigs: list
+    snapshot_qvec: np.ndarray
+    snapshot_tvec: np.ndarray
+    refine_relative_poses: Optional[int] = None
+    max_reproj_error: Optional[float] = None
+    _keep: list = field(default_factory=list, repr=False)
+
+    def struct(self) -> Rig:
+        r = Rig()
+        load().mi_ba_default_rig(C.byref(r))
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+        cam_off = i32(np.concatenate([[0], np.cumsum([len(g["cameras"]) for g in self.rigs])]))
+        cams = i32(np.concatenate([np.asarray(g["cameras"], np.int32) for g in self.rigs] + [np.zeros(0, np.int32)]))
+        ref = i32([g["ref_camera"] for g in self.rigs])
+        self.rel_qvec = np.ascontiguousarray(
+            np.concatenate([np.asarray(g["rel_qvec"], np.float64).reshape(-1, 4) for g in self.rigs]
+                           + [np.zeros((0, 4))]))
+        self.rel_tvec = np.ascontiguousarray(
+            np.concatenate([np.asarray(g["rel_tvec"], np.float64).reshape(-1, 3) for g in self.rigs]
+                           + [np.zeros((0, 3))]))
+        snaps = [sn for g in self.rigs for sn in g["snapshots"]]
+        rig_snap_off = i32(np.concatenate([[0], np.cumsum([len(g["snapshots"]) for g in self.rigs])]))
+        snap_off = i32(np.concatenate([[0], np.cumsum([len(sn) for sn in snaps])]))
+        snap_img = i32(np.concatenate([np.asarray(sn, np.int32) for sn in snaps] + [np.zeros(0, np.int32)]))
+        self.snapshot_qvec = np.ascontiguousarray(self.snapshot_qvec, dtype=np.float64).reshape(-1, 4)
+        self.snapshot_tvec = np.ascontiguousarray(self.snapshot_tvec, dtype=np.float64).reshape(-1, 3)
+        self._keep = [cam_off, cams, ref, rig_snap_off, snap_off, snap_img]
+        r.num_rigs = len(self.rigs)
+        r.rig_camera_off = _ptr(cam_off, _i32p)
+        r.rig_camera = _ptr(cams, _i32p)
+        r.rig_ref_camera = _ptr(ref, _i32p)
+        r.rel_qvec = _ptr(self.rel_qvec, _dp)
+        r.rel_tvec = _ptr(self.rel_tvec, _dp)
+        r.rig_snapshot_off = _ptr(rig_snap_off, _i32p)
+        r.num_snapshots = len(snaps)
+        r.snapshot_off = _ptr(snap_off, _i32p)
+        r.snapshot_image = _ptr(snap_img, _i32p)
+        r.snapshot_qvec = _ptr(self.snapshot_qvec, _dp)
+        r.snapshot_tvec = _ptr(self.snapshot_tvec, _dp)
+        if self.refine_relative_poses is not None:
+            r.refine_relative_poses = int(self.refine_relative_poses)
+        if self.max_reproj_error is not None:
+            r.max_reproj_error = float(self.max_reproj_error)
+        return r
+
+
+def rig_setup_stats(options: Options, scene: Scene, rig: RigInput) -> SetupInfo:
+    """mi_ba_rig_setup_stats: the rig problem's reduced-program counts (host only)."""
+    info = SetupInfo()
+    p = scene.problem()
+    r = rig.struct()
+    check(load().mi_ba_rig_setup_stats(C.byref(options), C.byref(p), C.byref(r), C.byref(info)),
+          "mi_ba_rig_setup_stats")
+    return info
+
+
+def rig_solve(options: Options, scene: Scene, rig: RigInput) -> Summary:
+    """mi_ba_rig_solve: RigBundleAdjuster::Solve.  The scene's parameter arrays
+    and rig.snapshot_qvec / snapshot_tvec / rel_qvec / rel_tvec are updated in place."""
+    s = Summary()
+    p = scene.problem()
+    r = rig.struct()
+    check(load().mi_ba_rig_solve(C.byref(options), C.byref(p), C.byref(r), C.byref(s)), "mi_ba_rig_solve")
+    return s
+
+
+def rig_evaluate(options: Options, scene: Scene, rig: "RigInput"):
+    """mi_ba_rig_evaluate -> (block_obs [n], residuals [n][2], jacobians [n][2][15 + c])."""
+    p = scene.problem()
+    r = rig.struct()
+    n = C.c_int64(0)
+    check(load().mi_ba_rig_evaluate(C.byref(options), C.byref(p), C.byref(r), 0, C.byref(n), None, None, None),
+          "mi_ba_rig_evaluate")
+    info = rig_setup_stats(options, scene, rig)
+    bo = np.empty(n.value, np.int64)
+    res = np.empty((n.value, 2), np.float64)
+    J = np.empty((n.value, 2, 15 + info.camera_tangent_size), np.float64)
+    check(load().mi_ba_rig_evaluate(C.byref(options), C.byref(p), C.byref(r), n.value, C.byref(n), _ptr(bo, _i64p),
+                                    _ptr(res, _dp), _ptr(J, _dp)), "mi_ba_rig_evaluate")
+    return bo, res, J
+
+
+def rig_project_chunk():
+    """(member pairs per chunk, member pairs per pass) of the rig projection kernel."""
+    lanes = C.c_int32(0)
+    chunk = load().mi_ba_rig_project_chunk(C.byref(lanes))
+    return int(chunk), int(lanes.value)
+
+
+def rig_reduce_dense(S: np.ndarray, b: Optional[np.ndarray], owner_slot, rel_slot, A, B, num_slots: int,
+                     num_intrinsics: int = 0, device: int = 0):
+    """mi_ba_rig_reduce_dense: S_rig = T^T S T (upper triangle; strict lower
+    zero) and b_rig = T^T b of the rig tangent map T given by the table."""
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    owner_slot = np.ascontiguousarray(owner_slot, dtype=np.int32)
+    rel_slot = np.ascontiguousarray(rel_slot, dtype=np.int32)
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    B = np.ascontiguousarray(B, dtype=np.float64)
+    t = RigTable()
+    t.num_images = len(owner_slot)
+    t.num_intrinsics = num_intrinsics
+    t.num_slots = num_slots
+    t.owner_slot = _ptr(owner_slot, _i32p)
+    t.rel_slot = _ptr(rel_slot, _i32p)
+    t.A = _ptr(A, _dp)
+    t.B = _ptr(B, _dp)
+    n_img = S.shape[0]
+    n_rig = 6 * num_slots + num_intrinsics
+    out = np.full((n_rig, n_rig), np.nan)
+    bb = None if b is None else np.ascontiguousarray(b, dtype=np.float64)
+    ob = None if b is None else np.full(n_rig, np.nan)
+    check(load().mi_ba_rig_reduce_dense(device, n_img, _ptr(S, _dp), _ptr(bb, _dp), C.byref(t), n_rig,
+                                        _ptr(out, _dp), _ptr(ob, _dp)), "mi_ba_rig_reduce_dense")
+    return out, ob
 
 
 @dataclass
@@ -816,17 +982,24 @@ def solve(options: Options, scene: Scene, semantic: Optional[SemanticInput] = No
 class Context:
     """Device-resident problem (mi_ba_context_*)."""
 
-    def __init__(self, options: Options, scene: Scene, semantic: Optional[SemanticInput] = None):
+    def __init__(self, options: Options, scene: Scene, semantic: Optional[SemanticInput] = None, rig=None):
         self.lib = load()
         self.options = options
         self.scene = scene
         self.semantic = semantic
+        self.rig = rig
+        self.h = None
         self._p = scene.problem()
         self._s = semantic.struct() if semantic is not None else None
+        sem = C.byref(self._s) if self._s is not None else None
         h = C.c_void_p()
-        check(self.lib.mi_ba_context_create(C.byref(options), C.byref(self._p),
-                                            C.byref(self._s) if self._s is not None else None, C.byref(h)),
-              "mi_ba_context_create")
+        if rig is not None:  # mi_ba_rig_context_create (rig: RigInput)
+            self._r = rig.struct()
+            check(self.lib.mi_ba_rig_context_create(C.byref(options), C.byref(self._p), sem, C.byref(self._r),
+                                                    C.byref(h)), "mi_ba_rig_context_create")
+        else:
+            check(self.lib.mi_ba_context_create(C.byref(options), C.byref(self._p), sem, C.byref(h)),
+                  "mi_ba_context_create")
         self.h = h
 
     def close(self):
