@@ -1,0 +1,179 @@
+// pose.h — RefineAbsolutePose of the reference (src/estimators/pose.h:93-124,
+// 185-198; pose.cc:198-322) on the MI355X: the reprojection error of the
+// inlier 2D-3D correspondences over the pose, optionally the focal length and
+// the extra parameters (the principal point stays fixed), Cauchy loss.
+//
+// Header-only facade over mi_ba_refine_absolute_pose_batch (mi_ba.h), plain
+// array types like the other facades.  RefineAbsolutePoses solves many
+// problems in one launch (one workgroup each, the whole LM on the device).
+// Where the reference CHECKs (options, the two size checks), this throws
+// std::invalid_argument; device errors throw std::runtime_error.
+//
+// Differences to the reference: a qvec that is not of unit length is
+// normalised first; the linear solve is a Cholesky of the normal equations,
+// not DENSE_QR.
+#pragma once
+
+#include <array>
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../mi_ba.h"
+#include "bundle_adjustment.h"
+
+namespace colmap_amd {
+
+struct AbsolutePoseRefinementOptions {
+  // Convergence criterion.
+  double gradient_tolerance = 1.0;
+  // Maximum number of solver iterations.
+  int max_num_iterations = 100;
+  // Scaling factor determines at which residual robustification takes place.
+  double loss_function_scale = 1.0;
+  // Whether to refine the focal length parameter group.
+  bool refine_focal_length = true;
+  // Whether to refine the extra parameter group.
+  bool refine_extra_params = true;
+  // Whether to print final summary.
+  bool print_summary = true;
+  // HIP device ordinal (build addition).
+  int device = 0;
+
+  void Check() const {
+    if (!(gradient_tolerance >= 0.0)) throw std::invalid_argument("gradient_tolerance must be >= 0");
+    if (max_num_iterations < 0) throw std::invalid_argument("max_num_iterations must be >= 0");
+    if (!(loss_function_scale >= 0.0)) throw std::invalid_argument("loss_function_scale must be >= 0");
+  }
+};
+
+// One problem of RefineAbsolutePoses: the arguments of RefineAbsolutePose.
+// rot_tvec_covariance (nullable): row-major 6 x 6, rotation tangent first,
+// then translation.
+struct AbsolutePoseProblem {
+  const std::vector<char>* inlier_mask = nullptr;
+  const std::vector<std::array<double, 2>>* points2D = nullptr;
+  const std::vector<std::array<double, 3>>* points3D = nullptr;
+  std::array<double, 4>* qvec = nullptr;
+  std::array<double, 3>* tvec = nullptr;
+  Camera* camera = nullptr;
+  std::array<double, 36>* rot_tvec_covariance = nullptr;
+};
+
+// Refines every problem in one call; returns per problem whether the solution
+// is usable (Ceres' IsSolutionUsable and, when asked for, a covariance that
+// could be computed).  summaries (nullable) receives the solver summaries.
+inline std::vector<bool> RefineAbsolutePoses(const AbsolutePoseRefinementOptions& options,
+                                             const std::vector<AbsolutePoseProblem>& problems,
+                                             std::vector<SolverSummary>* summaries = nullptr) {
+  options.Check();
+  const int n = (int)problems.size();
+  std::vector<int64_t> obs_off(n + 1, 0), cam_off(n + 1, 0);
+  bool any_cov = false;
+  for (int k = 0; k < n; ++k) {
+    const AbsolutePoseProblem& p = problems[k];
+    if (!p.inlier_mask || !p.points2D || !p.points3D || !p.qvec || !p.tvec || !p.camera)
+      throw std::invalid_argument("RefineAbsolutePose: null argument");
+    // CHECK_EQ(inlier_mask.size(), points2D.size()); CHECK_EQ(points2D.size(), points3D.size())
+    if (p.inlier_mask->size() != p.points2D->size()) throw std::invalid_argument("inlier_mask.size() != points2D.size()");
+    if (p.points2D->size() != p.points3D->size()) throw std::invalid_argument("points2D.size() != points3D.size()");
+    obs_off[k + 1] = obs_off[k] + (int64_t)p.points2D->size();
+    cam_off[k + 1] = cam_off[k] + (int64_t)p.camera->params.size();
+    any_cov = any_cov || p.rot_tvec_covariance;
+  }
+  if (summaries) summaries->assign(n, SolverSummary());
+  std::vector<bool> usable(n, false);
+  if (n == 0) return usable;
+  std::vector<double> p2(2 * (size_t)obs_off[n]), p3(3 * (size_t)obs_off[n]), cams((size_t)cam_off[n]), q(4 * (size_t)n),
+      t(3 * (size_t)n), cov(any_cov ? 36 * (size_t)n : 0);
+  std::vector<uint8_t> mask((size_t)obs_off[n]);
+  std::vector<int32_t> models(n);
+  for (int k = 0; k < n; ++k) {
+    const AbsolutePoseProblem& p = problems[k];
+    for (size_t i = 0; i < p.points2D->size(); ++i) {
+      const size_t o = (size_t)obs_off[k] + i;
+      p2[2 * o] = (*p.points2D)[i][0];
+      p2[2 * o + 1] = (*p.points2D)[i][1];
+      for (int m = 0; m < 3; ++m) p3[3 * o + m] = (*p.points3D)[i][m];
+      mask[o] = (*p.inlier_mask)[i] ? 1 : 0;
+    }
+    models[k] = p.camera->model_id;
+    for (size_t m = 0; m < p.camera->params.size(); ++m) cams[(size_t)cam_off[k] + m] = p.camera->params[m];
+    for (int m = 0; m < 4; ++m) q[4 * (size_t)k + m] = (*p.qvec)[m];
+    for (int m = 0; m < 3; ++m) t[3 * (size_t)k + m] = (*p.tvec)[m];
+  }
+  mi_ba_pose_refine_options o;
+  mi_ba_default_pose_refine_options(&o);
+  o.gradient_tolerance = options.gradient_tolerance;
+  o.max_num_iterations = options.max_num_iterations;
+  o.loss_function_scale = options.loss_function_scale;
+  o.refine_focal_length = options.refine_focal_length ? 1 : 0;
+  o.refine_extra_params = options.refine_extra_params ? 1 : 0;
+  o.device = options.device;
+  mi_ba_pose_batch b{};
+  b.num_problems = n;
+  b.obs_offsets = obs_off.data();
+  b.points2D = p2.data();
+  b.points3D = p3.data();
+  b.inlier_mask = mask.data();
+  b.camera_model_ids = models.data();
+  b.camera_param_offsets = cam_off.data();
+  b.camera_params = cams.data();
+  b.qvec = q.data();
+  b.tvec = t.data();
+  b.rot_tvec_covariance = any_cov ? cov.data() : nullptr;
+  std::vector<int32_t> statuses(n), ok(n);
+  std::vector<mi_ba_summary> sums(n);
+  const mi_ba_status st = mi_ba_refine_absolute_pose_batch(&o, &b, statuses.data(), sums.data(), ok.data());
+  if (st == MI_BA_ERR_INVALID_ARGUMENT) throw std::invalid_argument("RefineAbsolutePose: invalid argument");
+  if (st != MI_BA_OK) throw std::runtime_error(std::string("RefineAbsolutePose: ") + mi_ba_status_string(st));
+  for (int k = 0; k < n; ++k) {
+    const AbsolutePoseProblem& p = problems[k];
+    // camera_models.h:140-141 throws for an unknown model
+    if (statuses[k] == MI_BA_ERR_UNSUPPORTED) throw std::domain_error("Camera model does not exist");
+    if (statuses[k] != MI_BA_OK) throw std::runtime_error(std::string("RefineAbsolutePose: ") + mi_ba_status_string(statuses[k]));
+    SolverSummary s;
+    s.num_residuals_reduced = sums[k].num_residuals_reduced;
+    s.num_effective_parameters_reduced = sums[k].num_effective_parameters_reduced;
+    s.num_successful_steps = sums[k].num_successful_steps;
+    s.num_unsuccessful_steps = sums[k].num_unsuccessful_steps;
+    s.termination_type = (SolverSummary::TerminationType)sums[k].termination_type;
+    s.initial_cost = sums[k].initial_cost;
+    s.final_cost = sums[k].final_cost;
+    s.num_jacobian_evaluations = sums[k].num_jacobian_evaluations;
+    s.num_linear_solver_iterations = sums[k].num_linear_solver_iterations;
+    if (summaries) (*summaries)[k] = s;
+    // the library writes parameters back only where Ceres would
+    for (int m = 0; m < 4; ++m) (*p.qvec)[m] = q[4 * (size_t)k + m];
+    for (int m = 0; m < 3; ++m) (*p.tvec)[m] = t[3 * (size_t)k + m];
+    for (size_t m = 0; m < p.camera->params.size(); ++m) p.camera->params[m] = cams[(size_t)cam_off[k] + m];
+    if (p.rot_tvec_covariance && ok[k])
+      for (int m = 0; m < 36; ++m) (*p.rot_tvec_covariance)[m] = cov[36 * (size_t)k + m];
+    usable[k] = ok[k] != 0;
+    if (options.print_summary) {
+      PrintHeading2("Pose refinement report");
+      PrintSolverSummary(s);
+    }
+  }
+  return usable;
+}
+
+// RefineAbsolutePose (pose.cc:198-322), the reference's argument order.
+inline bool RefineAbsolutePose(const AbsolutePoseRefinementOptions& options, const std::vector<char>& inlier_mask,
+                               const std::vector<std::array<double, 2>>& points2D,
+                               const std::vector<std::array<double, 3>>& points3D, std::array<double, 4>* qvec,
+                               std::array<double, 3>* tvec, Camera* camera,
+                               std::array<double, 36>* rot_tvec_covariance = nullptr) {
+  AbsolutePoseProblem p;
+  p.inlier_mask = &inlier_mask;
+  p.points2D = &points2D;
+  p.points3D = &points3D;
+  p.qvec = qvec;
+  p.tvec = tvec;
+  p.camera = camera;
+  p.rot_tvec_covariance = rot_tvec_covariance;
+  return RefineAbsolutePoses(options, {p})[0];
+}
+
+}  // namespace colmap_amd

@@ -29,6 +29,9 @@
  *                              <- CalculateSquaredReprojectionError (src/base/projection.cc:111-128),
  *                                 Reconstruction::FilterPoints3DWithLargeReprojectionError
  *                                 (src/base/reconstruction.cc:1472-1525)
+ *   mi_ba_refine_absolute_pose_batch
+ *                              <- RefineAbsolutePose (src/estimators/pose.cc:198-322), many
+ *                                 problems per call
  *   mi_ba_semantic (struct)    <- SemanticBundleAdjustmentOptions depth/semantic maps
  *                                 (src/optim/semantic_bundle_adjustment.h:53-140,
  *                                 semantic_bundle_adjustment.cc:699-906,1021-1068)
@@ -764,6 +767,98 @@ mi_ba_status mi_ba_rig_reduce_dense(int32_t device, int32_t n_img, const double*
 /* Member pairs per chunk of the projection kernel; *lanes (nullable) = member
  * pairs of one pass of its member loop. */
 int32_t mi_ba_rig_project_chunk(int32_t* lanes);
+
+/* --- batched absolute-pose refinement -------------------------------------
+ * Additive entry points (MI_BA_ABI_VERSION stays 4).
+ * RefineAbsolutePose (src/estimators/pose.cc:198-322, called per registered
+ * image from sfm/incremental_mapper.cc:502): the reprojection residual of
+ * BundleAdjustmentCostFunction with every 3D point constant, a Cauchy loss,
+ * the pose on QuaternionManifold x R^3 and optionally the focal length and
+ * the extra parameters refined (the principal point never, pose.cc:251-257).
+ * Many such problems are solved in one launch: one workgroup per problem runs
+ * the whole Levenberg-Marquardt loop on the device.
+ *
+ * The three fields the reference sets on ceres::Solver::Options
+ * (gradient_tolerance, max_num_iterations, and the loss scale) are options;
+ * everything else is Ceres' default: function_tolerance 1e-6,
+ * parameter_tolerance 1e-8, max_num_consecutive_invalid_steps 5,
+ * initial_trust_region_radius 1e4, min_relative_decrease 1e-3, monotonic
+ * steps, Jacobi scaling.  The linear solve is a Cholesky of the normal
+ * equations (the reference: DENSE_QR). */
+typedef struct mi_ba_pose_refine_options {
+  double gradient_tolerance;        /* default 1.0 */
+  int32_t max_num_iterations;       /* default 100 */
+  double loss_function_scale;       /* default 1.0 (CauchyLoss) */
+  int32_t refine_focal_length;      /* default 1 */
+  int32_t refine_extra_params;      /* default 1 */
+  int32_t device;                   /* HIP device ordinal, default 0 */
+} mi_ba_pose_refine_options;
+
+/* Zeroes the struct (padding included), then sets the defaults above. */
+void mi_ba_default_pose_refine_options(mi_ba_pose_refine_options* options);
+
+/* A batch of problems as a struct of arrays.  Problem k owns the
+ * correspondences obs_offsets[k] .. obs_offsets[k + 1) of points2D /
+ * points3D / inlier_mask and the camera parameters camera_param_offsets[k] ..
+ * camera_param_offsets[k + 1) (mi_ba_num_params(camera_model_ids[k]) of
+ * them).  A qvec that is not of unit length is normalised first (as
+ * BundleAdjuster::SetUp does; the reference's RefineAbsolutePose does not). */
+typedef struct mi_ba_pose_batch {
+  int32_t num_problems;
+  const int64_t* obs_offsets;          /* [num_problems + 1] */
+  const double* points2D;              /* [obs_offsets[n]][2] */
+  const double* points3D;              /* [obs_offsets[n]][3] */
+  const uint8_t* inlier_mask;          /* nullable (= all inliers); [obs_offsets[n]], nonzero = used */
+  const int32_t* camera_model_ids;     /* [num_problems] MI_BA_* model id */
+  const int64_t* camera_param_offsets; /* [num_problems + 1] */
+  double* camera_params;               /* (in/out) */
+  double* qvec;                        /* (in/out) [num_problems][4] (w,x,y,z) */
+  double* tvec;                        /* (in/out) [num_problems][3] */
+  double* rot_tvec_covariance;         /* nullable (out) [num_problems][36] row-major 6 x 6 */
+} mi_ba_pose_batch;
+
+/* Solves every problem of the batch.  Per problem k: statuses[k] (MI_BA_OK,
+ * or MI_BA_ERR_UNSUPPORTED for a camera model outside the nine supported:
+ * that problem is skipped), summaries[k] (initial / final cost, successful
+ * and unsuccessful steps, termination type, num_residuals_reduced = twice the
+ * inliers, num_effective_parameters_reduced) and usable[k] = Ceres'
+ * IsSolutionUsable (CONVERGENCE, NO_CONVERGENCE or USER_SUCCESS) and, with
+ * rot_tvec_covariance, a covariance that could be computed.  Parameters are
+ * written back unless the problem ends in MI_BA_FAILURE (a non-finite initial
+ * cost: usable 0, parameters untouched).  A problem without inliers does
+ * nothing: CONVERGENCE, usable 1, covariance untouched.
+ * rot_tvec_covariance: the pose block (rotation tangent first, then
+ * translation) of the inverse of J'J at the final point, J the loss-corrected
+ * tangent Jacobian over pose and refined intrinsics, undamped and unscaled
+ * (ceres::Covariance with apply_loss_function); a pivot of its Cholesky that
+ * is not above 1e-14 of the column's own diagonal entry (rank deficiency)
+ * leaves the 36 values untouched and makes the problem not usable, as
+ * covariance.Compute returning false does (pose.cc:311-313).
+ * The call itself fails only on invalid arguments or device errors.  Every
+ * sum runs in a fixed order: the same problem gives the same bits on every
+ * run and at every position of a batch. */
+mi_ba_status mi_ba_refine_absolute_pose_batch(const mi_ba_pose_refine_options* options,
+                                              const mi_ba_pose_batch* batch, int32_t* statuses,
+                                              mi_ba_summary* summaries, int32_t* usable);
+
+/* Refined intrinsics of a model under the two flags: writes the parameter
+ * indices (camera_models.h FocalLengthIdxs, then ExtraParamsIdxs) into
+ * idxs[8] and returns their number (0: pose only), or -1 for an unsupported
+ * model.  Host only. */
+int32_t mi_ba_pose_refine_intrinsics(int32_t camera_model, int32_t refine_focal_length,
+                                     int32_t refine_extra_params, int32_t* idxs);
+
+/* Most inlier correspondences of one problem that the kernel keeps resident
+ * in LDS; a problem with more streams them from device memory. */
+int32_t mi_ba_pose_refine_lds_capacity(void);
+
+/* Diagnostic (parity tests): while a trace buffer is set, every batch call
+ * records the outcome of LM iteration i (1-based) of problem k in
+ * trace[k * capacity + i - 1]: bit 0 step valid, bit 1 step successful, bit 2
+ * the iteration ended the solve; 0xFF for iterations that did not run (and
+ * for skipped problems).  The buffer must hold num_problems * capacity bytes;
+ * NULL switches it off.  Process-wide: not for concurrent callers. */
+void mi_ba_pose_refine_set_trace(uint8_t* trace, int32_t capacity);
 
 /* Per-kernel HIP-event timing on the context's stream (enabled with
  * mi_ba_set_timing).  name: "reproj_jacobian", "semantic_jacobian", ... */

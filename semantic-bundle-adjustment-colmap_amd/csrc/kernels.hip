@@ -16,6 +16,7 @@
 #include "ba_math.h"
 #include "device.h"
 #include "kernels.h"
+#include "reproj_block.h"
 #include "step_bodies.h"
 
 namespace miba {
@@ -125,45 +126,12 @@ __device__ inline double block_cost(const DevProblem& p, const double* __restric
   return 0.5 * rho[0];
 }
 
-// Refined-intrinsics mask per model and refine flags (bit 0 focal, bit 1
-// principal point, bit 2 extra params): camera_models.h *Idxs, and
-// BundleAdjuster::ParameterizeCameras (bundle_adjustment.cc:480-516).
-__host__ __device__ constexpr unsigned cam_tangent_mask(int M, int RF) {
-  unsigned f = 0, pp = 0, ex = 0;
-  if (M == kSimplePinhole) { f = 0x1; pp = 0x6; ex = 0x0; }
-  if (M == kPinhole) { f = 0x3; pp = 0xC; ex = 0x0; }
-  if (M == kSimpleRadial) { f = 0x1; pp = 0x6; ex = 0x8; }
-  if (M == kRadial) { f = 0x1; pp = 0x6; ex = 0x18; }
-  if (M == kOpenCV) { f = 0x3; pp = 0xC; ex = 0xF0; }
-  return ((RF & 1) ? f : 0u) | ((RF & 2) ? pp : 0u) | ((RF & 4) ? ex : 0u);
-}
-// The same over all nine models (camera_models.h: OPENCV_FISHEYE and FOV
-// fx fy cx cy + extras, the RADIAL_FISHEYEs f cx cy + extras).  The run-time
-// callers of the five-model kernels keep cam_tangent_mask.
-__host__ __device__ constexpr unsigned cam_tangent_mask_all(int M, int RF) {
-  unsigned f = 0, pp = 0, ex = 0;
-  if (M == kOpenCVFisheye) { f = 0x3; pp = 0xC; ex = 0xF0; }
-  else if (M == kFOV) { f = 0x3; pp = 0xC; ex = 0x10; }
-  else if (M == kSimpleRadialFisheye) { f = 0x1; pp = 0x6; ex = 0x8; }
-  else if (M == kRadialFisheye) { f = 0x1; pp = 0x6; ex = 0x18; }
-  else return cam_tangent_mask(M, RF);
-  return ((RF & 1) ? f : 0u) | ((RF & 2) ? pp : 0u) | ((RF & 4) ? ex : 0u);
-}
-__host__ __device__ constexpr int popcount8(unsigned m) {
-  return (int)((m & 1) + ((m >> 1) & 1) + ((m >> 2) & 1) + ((m >> 3) & 1) + ((m >> 4) & 1) + ((m >> 5) & 1) +
-               ((m >> 6) & 1) + ((m >> 7) & 1));
-}
-
 // Jacobian entries of one block row (rw = 0: x, 1: y) into dst[0..W).
 // Columns: rotation tangent (3), translation (3), point (3), refined
 // intrinsics (CT, SubsetManifold PlusJacobian = column selection).
 __device__ inline void emit_row_pose_point(int rw, double* dst, const double (&B)[6], const double (&Mq)[9],
                                            bool pose_var, uint32_t flags, const double (&jx)[2][3]) {
-#pragma unroll
-  for (int b = 0; b < 3; ++b)
-    dst[b] = pose_var ? B[rw * 3 + 0] * Mq[b] + B[rw * 3 + 1] * Mq[3 + b] + B[rw * 3 + 2] * Mq[6 + b] : 0.0;
-#pragma unroll
-  for (int b = 0; b < 3; ++b) dst[3 + b] = (pose_var && !((flags >> (1 + b)) & 1u)) ? B[rw * 3 + b] : 0.0;
+  emit_row_pose(rw, dst, B, Mq, pose_var, flags);  // reproj_block.h
 #pragma unroll
   for (int b = 0; b < 3; ++b) dst[6 + b] = jx[rw][b];
 }
@@ -543,34 +511,15 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WPE))) void 
         sc = sqrt(rho[1]);
       }
       // B = d(x,y)/dP (2x3) = A * d(u,v)/dP, loss-scaled
-      B[0] = A[0] * iz; B[1] = A[1] * iz; B[2] = -(A[0] * u + A[1] * v) * iz;
-      B[3] = A[2] * iz; B[4] = A[3] * iz; B[5] = -(A[2] * u + A[3] * v) * iz;
+      reproj_dpixel_dpoint(A, iz, u, v, B);
       if constexpr (LOSS != 0) {
   #pragma unroll
         for (int k = 0; k < 6; ++k) B[k] *= sc;
       }
-      // d(R X)/d(tangent) of QuaternionManifold (plus = q_delta * q, rotation
-      // angle 2|delta|) = -2 [R X]x: the product Dq * PlusJacobian below in
-      // closed form, equal up to rounding for a unit q (the general product
-      // serves a quaternion that is not normalised, as AutoDiff would)
-      const bool unit_q =
-          (D & 512) && ((D & 4096) || ((D & 2048) ? unit_rec
-                                                  : fabs(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] - 1.0) <= 1e-12));
-      if (pose_var && unit_q) {
-        Mq[0] = 0.0;       Mq[1] = 2.0 * a2;  Mq[2] = -2.0 * a1;
-        Mq[3] = -2.0 * a2; Mq[4] = 0.0;       Mq[5] = 2.0 * a0;
-        Mq[6] = 2.0 * a1;  Mq[7] = -2.0 * a0; Mq[8] = 0.0;
-      } else if (pose_var) {
-        double Dq[12], PJ[12];
-        unit_quat_rotate_dq(q, X, Dq);
-        quat_plus_jacobian(q, PJ);
-  #pragma unroll
-        for (int a = 0; a < 3; ++a)
-  #pragma unroll
-          for (int b = 0; b < 3; ++b)
-            Mq[a * 3 + b] = Dq[a * 4 + 0] * PJ[0 * 3 + b] + Dq[a * 4 + 1] * PJ[1 * 3 + b] +
-                            Dq[a * 4 + 2] * PJ[2 * 3 + b] + Dq[a * 4 + 3] * PJ[3 * 3 + b];
-      }
+      // d(R X)/d(tangent) of QuaternionManifold: closed form for a unit q,
+      // the general product otherwise (reproj_block.h)
+      const bool unit_q = (D & 512) && ((D & 4096) || ((D & 2048) ? unit_rec : quat_is_unit(q)));
+      rotation_tangent_jacobian(q, X, a0, a1, a2, pose_var, unit_q, Mq);
       if (ptv) {
         double R[9];
         if constexpr ((D & (1024 | 2048)) != 0) {

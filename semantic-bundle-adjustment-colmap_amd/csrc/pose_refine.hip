@@ -1,0 +1,880 @@
+// pose_refine.hip — batched absolute-pose refinement (product code).
+//
+//   mi_ba_refine_absolute_pose_batch  <- RefineAbsolutePose
+//                                        (src/estimators/pose.cc:198-322)
+//
+// One workgroup per problem; the whole Levenberg-Marquardt solve (Ceres 2.1
+// TrustRegionMinimizer with its default options, restated as in runtime.hip
+// context_solve) runs inside pose_refine_kernel with no host round trip.
+//
+// Per linearization the four waves stride over the problem's observations in
+// tiles of 64 (tile t belongs to wave t % 4).  Each lane evaluates the
+// residual and the loss-corrected tangent Jacobian of its observation with
+// the chain rule the reprojection kernel uses (reproj_block.h, ba_math.h) and
+// writes its two rows, as the columns of the augmented matrix [J r], into the
+// wave's LDS slab: column c holds 128 values (row x of the 64 observations,
+// then row y).  Every lane owns one or two entries (i, j) of the upper
+// triangle of [J r]'[J r] — J'J, the gradient J'r and r'r — and sums the
+// slab's 128 products in order, so the accumulators never leave two
+// registers per lane.  Waves are combined in wave order: every sum has a
+// fixed order and no atomics, the same input gives the same bits.
+//
+// LDS banking (64 banks of 4 B): a column has a stride of 129 doubles, so
+// the lanes' column reads (i * 129 + k) fall on banks 2 i + 2 k mod 64 — at
+// most 15 distinct columns, no conflict; lanes that share a column read one
+// address (broadcast).  The row writes are consecutive doubles.
+//
+// Wave 0 then runs the small solve with lane i owning row i of the system
+// (at most 14 x 14): Jacobi scaling, LM damping, a right-looking Cholesky
+// whose column broadcasts are wave shuffles, the two triangular solves, the
+// model cost change and the candidate point.  A second pass over the
+// observations gives the candidate cost.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/mi_ba.h"
+#include "ba_math.h"
+#include "reproj_block.h"
+
+namespace miba {
+namespace {
+
+constexpr int kPoseTB = 256;
+constexpr int kPoseWaves = kPoseTB / 64;
+// Most observations kept in LDS (5 doubles each: 80 KiB of the CU's 160 KiB,
+// beside 70 KiB of slabs and system at the 14-wide instantiation).
+constexpr int kPoseLdsObs = 2048;
+constexpr int kColStride = 129;
+
+// Ceres defaults RefineAbsolutePose leaves alone (solver.h).
+constexpr double kFunctionTolerance = 1e-6;
+constexpr double kParameterTolerance = 1e-8;
+constexpr int kMaxConsecutiveInvalid = 5;
+constexpr double kInitialRadius = 1e4;
+constexpr double kMinRelativeDecrease = 1e-3;
+constexpr double kMinRadius = 1e-32;
+constexpr double kMaxRadius = 1e16;
+// covariance: a pivot at or below this fraction of the column's own diagonal
+// entry is rank deficiency
+constexpr double kCovPivotTolerance = 1e-14;
+
+struct PoseProblemDev {
+  int64_t obs_begin;  // into the compacted correspondence arrays
+  int32_t count;      // inliers
+  int32_t model;
+  int32_t ct;         // refined intrinsics (0: pose only)
+  int32_t np;         // camera parameters
+  int32_t idx[8];     // refined parameter indices
+  int32_t index;      // problem index of the batch (state / out / cov rows)
+  int32_t pad;
+};
+
+constexpr int kOutStride = 8;  // initial cost, final cost, successful, unsuccessful, termination, covariance ok
+
+struct PoseArgs {
+  const PoseProblemDev* prob;
+  const double2* p2;
+  const double* p3;
+  double* state;  // [n][16] q(4) t(3) pad params(8), in/out
+  double* out;    // [n][kOutStride]
+  double* cov;    // nullable [n][36]
+  double gradient_tolerance;
+  double loss_scale;
+  int32_t max_num_iterations;
+  int32_t lds_obs;  // observations the launch's LDS holds
+  uint8_t* trace;   // nullable [n][trace_cap]: outcome of each LM iteration (mi_ba_pose_refine_set_trace)
+  int32_t trace_cap;
+};
+
+enum { kActStop = 0, kActEval = 1, kActAccept = 2, kActReject = 3 };
+
+// trace byte of iteration it (1-based): bit 0 step valid, bit 1 successful,
+// bit 2 the iteration ended the solve
+__device__ __forceinline__ void pose_trace(const PoseArgs& a, int index, int it, int valid, int successful, int end) {
+  if (a.trace && it >= 1 && it <= a.trace_cap)
+    a.trace[(size_t)index * a.trace_cap + it - 1] = (uint8_t)(valid | successful << 1 | end << 2);
+}
+
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// xor tree: the same order on every run
+__device__ __forceinline__ double wave_sum_fixed(double v) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+struct PoseObsSource {
+  const double* sx;  // LDS, SoA (resident) ...
+  const double2* p2; // ... or device memory
+  const double* p3;
+  bool resident;
+  int lds_obs;
+  __device__ __forceinline__ void load(int i, double* ox, double* oy, double X[3]) const {
+    if (resident) {
+      *ox = sx[i];
+      *oy = sx[lds_obs + i];
+      X[0] = sx[2 * lds_obs + i];
+      X[1] = sx[3 * lds_obs + i];
+      X[2] = sx[4 * lds_obs + i];
+    } else {
+      const double2 o = p2[i];
+      *ox = o.x;
+      *oy = o.y;
+      X[0] = p3[3 * (size_t)i];
+      X[1] = p3[3 * (size_t)i + 1];
+      X[2] = p3[3 * (size_t)i + 2];
+    }
+  }
+};
+
+// Cost 0.5 rho(|r|^2) of one observation at the parameters st (q t pad params).
+__device__ inline double pose_obs_cost(int model, const double* st, double loss_scale, double ox, double oy,
+                                       const double X[3]) {
+  const double q[4] = {st[0], st[1], st[2], st[3]};
+  double prm[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) prm[k] = st[8 + k];
+  double P[3];
+  unit_quat_rotate(q, X, P);
+  P[0] += st[4];
+  P[1] += st[5];
+  P[2] += st[6];
+  const double iz = 1.0 / P[2];
+  double x, y;
+  world_to_image_all(model, prm, P[0] * iz, P[1] * iz, &x, &y);
+  const double r0 = x - ox, r1 = y - oy;
+  double rho[3];
+  loss_eval(kLossCauchy, loss_scale, r0 * r0 + r1 * r1, rho);
+  return 0.5 * rho[0];
+}
+
+// Residual, loss-corrected tangent rows (rotation 3, translation 3, refined
+// intrinsics NT - 6) and cost of one observation: the arithmetic of
+// reproj_jacobian_kernel for a variable pose and a constant point.
+template <int NT>
+__device__ inline void pose_obs_rows(int model, const double* st, const int* idx, int ct, double loss_scale, double ox,
+                                     double oy, const double X[3], double (&J0)[NT + 1], double (&J1)[NT + 1],
+                                     double* cost) {
+  const double q[4] = {st[0], st[1], st[2], st[3]};
+  double prm[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) prm[k] = st[8 + k];
+  double P[3];
+  unit_quat_rotate(q, X, P);
+  const double a0 = P[0], a1 = P[1], a2 = P[2];  // R X
+  P[0] += st[4];
+  P[1] += st[5];
+  P[2] += st[6];
+  const double iz = 1.0 / P[2];
+  const double u = P[0] * iz, v = P[1] * iz;
+  double x, y, A[4], Jp8[16];
+  world_to_image_jac_all(model, prm, u, v, &x, &y, A, Jp8);
+  const double r0 = x - ox, r1 = y - oy;
+  double rho[3];
+  loss_eval(kLossCauchy, loss_scale, r0 * r0 + r1 * r1, rho);
+  *cost = 0.5 * rho[0];
+  // Ceres Corrector, rho'' <= 0 branch: r, J *= sqrt(rho')
+  const double sc = sqrt(rho[1]);
+  double B[6], Mq[9];
+  reproj_dpixel_dpoint(A, iz, u, v, B);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) B[k] *= sc;
+  rotation_tangent_jacobian(q, X, a0, a1, a2, true, quat_is_unit(q), Mq);
+  emit_row_pose(0, J0, B, Mq, true, 0u);
+  emit_row_pose(1, J1, B, Mq, true, 0u);
+  if constexpr (NT > 6) {
+#pragma unroll
+    for (int m = 0; m < NT - 6; ++m) {
+      double v0 = 0.0, v1 = 0.0;
+      const int im = m < ct ? idx[m] : -1;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        v0 = im == k ? Jp8[k] : v0;
+        v1 = im == k ? Jp8[8 + k] : v1;
+      }
+      J0[6 + m] = v0 * sc;
+      J1[6 + m] = v1 * sc;
+    }
+  }
+  J0[NT] = r0 * sc;
+  J1[NT] = r1 * sc;
+}
+
+// Total of the per-thread costs in sCost (wave 0; every lane gets the sum).
+__device__ inline double pose_cost_total(const double* sCost, int lane) {
+  double c = sCost[lane];
+#pragma unroll
+  for (int w = 1; w < kPoseWaves; ++w) c += sCost[64 * w + lane];
+  return wave_sum_fixed(c);
+}
+
+// Dense Cholesky by one wave, in LDS: lane i < NT owns row i of the lower
+// triangle in sA (row stride NT + 1: the lanes' rows start on distinct even
+// banks); on return sA holds L.  A pivot k with !(pivot > tol * d0[k]) makes
+// the result false.  Column k reaches the other rows through LDS.
+template <int NT>
+__device__ inline bool wave_cholesky(double* sA, int lane, double tol, const double* d0) {
+  constexpr int S = NT + 1;
+  bool ok = true;
+#pragma unroll 1
+  for (int k = 0; k < NT; ++k) {
+    wave_sync();
+    const double akk = sA[k * S + k];
+    if (!(akk > tol * d0[k])) ok = false;
+    const double lkk = sqrt(akk);
+    const bool mine = lane < NT && lane >= k;
+    double lik = 0.0;
+    if (mine) lik = lane == k ? lkk : sA[lane * S + k] / lkk;
+    wave_sync();
+    if (mine) sA[lane * S + k] = lik;
+    wave_sync();
+    if (mine)
+      for (int j = k + 1; j <= lane; ++j) sA[lane * S + j] -= lik * sA[j * S + k];
+  }
+  wave_sync();
+  return ok;
+}
+
+// Solves L L' x = b with L in sA: lane i < NT passes b_i and receives x_i;
+// sx (NT doubles of LDS) carries each solved component to the other lanes.
+template <int NT>
+__device__ inline double wave_chol_solve(const double* sA, double b, int lane, double* sx) {
+  constexpr int S = NT + 1;
+#pragma unroll 1
+  for (int k = 0; k < NT; ++k) {
+    if (lane == k) sx[k] = b / sA[k * S + k];
+    wave_sync();
+    const double yk = sx[k];
+    if (lane == k) b = yk;
+    else if (lane > k && lane < NT) b -= sA[lane * S + k] * yk;
+  }
+#pragma unroll 1
+  for (int k = NT - 1; k >= 0; --k) {
+    if (lane == k) sx[k] = b / sA[k * S + k];
+    wave_sync();
+    const double xk = sx[k];
+    if (lane == k) b = xk;
+    else if (lane < k) b -= sA[k * S + lane] * xk;
+  }
+  wave_sync();
+  return b;
+}
+
+// LM state of one problem, in LDS: read and written by wave 0 only, so no
+// register holds it across the observation passes.
+struct PoseLm {
+  double x_cost, initial_cost, radius, decrease_factor;
+  double model_cost_change, x_norm, step_norm, pad;
+  int iteration, consecutive_invalid, n_successful, n_unsuccessful;
+  int termination, last_successful, action0, action1;
+};
+
+template <int NT>
+constexpr int pose_lds_doubles(int lds_obs) {
+  constexpr int NC = NT + 1;
+  return kPoseWaves * NC * kColStride + kPoseWaves * 128 + NC * NC + kPoseTB + 16 + 16 + NT * (NT + 1) + 3 * 16 +
+         (int)(sizeof(PoseLm) / 8) + 8 + 5 * lds_obs;
+}
+
+template <int NT>
+__global__ __launch_bounds__(kPoseTB) void pose_refine_kernel(PoseArgs a) {
+  constexpr int NC = NT + 1;
+  constexpr int NE = NC * (NC + 1) / 2;
+  constexpr int EPL = (NE + 63) / 64;
+  extern __shared__ double lds[];
+  double* slab_all = lds;
+  double* red = slab_all + kPoseWaves * NC * kColStride;
+  double* sM = red + kPoseWaves * 128;  // [NC][NC] symmetric [J r]'[J r]
+  double* sCost = sM + NC * NC;
+  double* sState = sCost + kPoseTB;
+  double* sCand = sState + 16;
+  double* sA = sCand + 16;              // [NT][NT + 1] system / factor
+  double* sScale = sA + NT * (NT + 1);  // Jacobi scaling per column, from the first Jacobian
+  double* sStep = sScale + 16;
+  double* sD0 = sStep + 16;
+  PoseLm* lm = reinterpret_cast<PoseLm*>(sD0 + 16);
+  int* sIdx = reinterpret_cast<int*>(reinterpret_cast<double*>(lm) + sizeof(PoseLm) / 8);
+  double* sObs = reinterpret_cast<double*>(sIdx) + 8;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const PoseProblemDev* pb = a.prob + blockIdx.x;
+  const int count = pb->count, model = pb->model, ct = pb->ct, n = 6 + ct, index = pb->index;
+  double* out = a.out + (size_t)index * kOutStride;
+  if (count <= 0) {  // nothing to do: CONVERGENCE, parameters as they are
+    if (tid == 0) {
+      out[0] = 0.0; out[1] = 0.0; out[2] = 0.0; out[3] = 0.0; out[4] = MI_BA_CONVERGENCE; out[5] = 0.0;
+    }
+    return;
+  }
+  PoseObsSource src;
+  src.lds_obs = a.lds_obs;
+  src.resident = count <= a.lds_obs;
+  src.sx = sObs;
+  src.p2 = a.p2 + pb->obs_begin;
+  src.p3 = a.p3 + 3 * pb->obs_begin;
+  if (src.resident) {
+    for (int i = tid; i < count; i += kPoseTB) {
+      const double2 o = src.p2[i];
+      sObs[i] = o.x;
+      sObs[a.lds_obs + i] = o.y;
+      sObs[2 * a.lds_obs + i] = src.p3[3 * (size_t)i];
+      sObs[3 * a.lds_obs + i] = src.p3[3 * (size_t)i + 1];
+      sObs[4 * a.lds_obs + i] = src.p3[3 * (size_t)i + 2];
+    }
+  }
+  if (tid < 16) sState[tid] = a.state[(size_t)index * 16 + tid];
+  if (tid < 8) sIdx[tid] = pb->idx[tid];
+  if (tid == 0) {
+    lm->radius = kInitialRadius;
+    lm->decrease_factor = 2.0;
+    lm->iteration = 0;
+    lm->consecutive_invalid = 0;
+    lm->n_successful = 0;
+    lm->n_unsuccessful = 0;
+    lm->termination = MI_BA_NO_CONVERGENCE;
+    lm->last_successful = 1;  // iteration 0 counts as successful (IterationZero)
+  }
+  __syncthreads();
+
+  // the lane's entries (i, j), i <= j < NC, of the upper triangle
+  int ei[EPL], ej[EPL];
+#pragma unroll
+  for (int s = 0; s < EPL; ++s) {
+    int e = lane + 64 * s, i = 0, w = NC;
+    if (e >= NE) e = 0;  // idle slot: sums entry 0, never stored
+    while (e >= w) { e -= w; --w; ++i; }
+    ei[s] = i;
+    ej[s] = i + e;
+  }
+
+  bool first = true;
+  int action = kActAccept;  // the first pass linearizes at the given point
+  while (true) {
+    if (action == kActAccept) {
+      // [J r]'[J r] and the cost at sState -> sM
+      double* slab = slab_all + wave * NC * kColStride;
+      int idx[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) idx[k] = sIdx[k];
+      double acc[EPL];
+#pragma unroll
+      for (int s = 0; s < EPL; ++s) acc[s] = 0.0;
+      double cost_acc = 0.0;
+      for (int tile = wave; tile * 64 < count; tile += kPoseWaves) {
+        const int i = tile * 64 + lane;
+        {
+          double J0[NC], J1[NC];
+#pragma unroll
+          for (int c = 0; c < NC; ++c) { J0[c] = 0.0; J1[c] = 0.0; }
+          if (i < count) {
+            double ox, oy, X[3], cost;
+            src.load(i, &ox, &oy, X);
+            pose_obs_rows<NT>(model, sState, idx, ct, a.loss_scale, ox, oy, X, J0, J1, &cost);
+            cost_acc += cost;
+          }
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            slab[c * kColStride + lane] = J0[c];
+            slab[c * kColStride + 64 + lane] = J1[c];
+          }
+        }
+        wave_sync();
+#pragma unroll
+        for (int s = 0; s < EPL; ++s) {
+          const double* ci = slab + ei[s] * kColStride;
+          const double* cj = slab + ej[s] * kColStride;
+          double v = acc[s];
+#pragma unroll 4
+          for (int k = 0; k < 128; ++k) v += ci[k] * cj[k];
+          acc[s] = v;
+        }
+        wave_sync();
+      }
+#pragma unroll
+      for (int s = 0; s < EPL; ++s) red[wave * 128 + lane + 64 * s] = acc[s];
+      sCost[tid] = cost_acc;
+      __syncthreads();
+      if (wave == 0) {
+#pragma unroll
+        for (int s = 0; s < EPL; ++s) {
+          const int e = lane + 64 * s;
+          if (e < NE) {
+            double v = red[e];
+#pragma unroll
+            for (int w = 1; w < kPoseWaves; ++w) v += red[w * 128 + e];
+            sM[ei[s] * NC + ej[s]] = v;
+            sM[ej[s] * NC + ei[s]] = v;
+          }
+        }
+        const double total = pose_cost_total(sCost, lane);
+        wave_sync();
+        if (first) {
+          if (lane < 16) sScale[lane] = lane < n ? 1.0 / (1.0 + sqrt(sM[lane * NC + lane])) : 1.0;
+          if (lane == 0) {
+            lm->x_cost = total;
+            lm->initial_cost = total;
+          }
+          wave_sync();
+        }
+      }
+      first = false;
+    }
+
+    if (wave == 0) {
+      int act = kActStop;
+      // a non-finite initial cost: FAILURE, parameters untouched
+      bool go = isfinite(lm->x_cost);
+      if (!go && lane == 0) lm->termination = MI_BA_FAILURE;
+      while (go) {
+        // FinalizeIterationAndCheckIfMinimizerCanContinue
+        if (lm->iteration >= a.max_num_iterations) {
+          if (lane == 0) lm->termination = MI_BA_NO_CONVERGENCE;
+          break;
+        }
+        if (lm->last_successful) {
+          // GradientToleranceReached: |x - Plus(x, -g)|_inf, g = J'r
+          const double d[3] = {-sM[0 * NC + NT], -sM[1 * NC + NT], -sM[2 * NC + NT]};
+          const double q[4] = {sState[0], sState[1], sState[2], sState[3]};
+          double qn[4], gmax = 0.0;
+          quat_plus(q, d, qn);
+#pragma unroll
+          for (int m = 0; m < 4; ++m) gmax = fmax(gmax, fabs(q[m] - qn[m]));
+          for (int m = 0; m < 3; ++m) gmax = fmax(gmax, fabs(sState[4 + m] - (sState[4 + m] + -sM[(3 + m) * NC + NT])));
+          for (int m = 0; m < ct; ++m) {
+            const double xv = sState[8 + sIdx[m]];
+            gmax = fmax(gmax, fabs(xv - (xv + -sM[(6 + m) * NC + NT])));
+          }
+          if (gmax <= a.gradient_tolerance) {
+            if (lane == 0) lm->termination = MI_BA_CONVERGENCE;
+            break;
+          }
+        }
+        const double radius = lm->radius;
+        if (radius <= kMinRadius) {
+          if (lane == 0) lm->termination = MI_BA_CONVERGENCE;
+          break;
+        }
+        wave_sync();
+        if (lane == 0) lm->iteration += 1;
+        // row `lane` of the scaled, damped system (rows past n: identity);
+        // LM diagonal: the clipped scaled column norm over the radius
+        const double scale = lane < 16 ? sScale[lane] : 1.0;
+        double gs = 0.0;
+        if (lane < NT) {
+          for (int j = 0; j <= lane; ++j) {
+            double v = (lane < n) ? sM[lane * NC + j] * scale * sScale[j] : 0.0;
+            if (j == lane) v = lane < n ? v + fmin(fmax(v, 1e-6), 1e32) / radius : 1.0;
+            sA[lane * (NT + 1) + j] = v;
+          }
+          sD0[lane] = 1.0;
+          if (lane < n) gs = sM[lane * NC + NT] * scale;
+        }
+        bool ok = wave_cholesky<NT>(sA, lane, 0.0, sD0);
+        double step = 0.0, model = 0.0;
+        if (ok) {
+          // Ceres solves (J'J + D'D) x = J'r, step = -x
+          step = -wave_chol_solve<NT>(sA, gs, lane, sStep);
+          if (lane < 16) sStep[lane] = lane < n ? step : 0.0;
+          wave_sync();
+          double term = 0.0;
+          if (lane < n) {
+            double hstep = 0.0;
+            for (int j = 0; j < n; ++j) hstep += sM[lane * NC + j] * scale * sScale[j] * sStep[j];
+            term = step * (gs + 0.5 * hstep);
+          }
+          model = -wave_sum_fixed(term);
+          ok = isfinite(model) && model > 0.0;
+        }
+        if (!ok) {
+          const int inv = lm->consecutive_invalid + 1;
+          const double df = lm->decrease_factor;
+          wave_sync();
+          if (lane == 0) {
+            lm->last_successful = 0;
+            lm->consecutive_invalid = inv;
+            lm->n_unsuccessful += 1;
+            lm->radius = radius / df;
+            lm->decrease_factor = df * 2.0;
+            if (inv > kMaxConsecutiveInvalid) lm->termination = MI_BA_FAILURE;
+            pose_trace(a, index, lm->iteration, 0, 0, inv > kMaxConsecutiveInvalid ? 1 : 0);
+          }
+          wave_sync();
+          if (inv > kMaxConsecutiveInvalid) break;
+          continue;
+        }
+        // candidate = Plus(x, step * scale)
+        const double delta = step * scale;
+        if (lane < 16) {
+          sCand[lane] = sState[lane];
+          sStep[lane] = lane < n ? delta : 0.0;
+        }
+        wave_sync();
+        {
+          const double dq[3] = {sStep[0], sStep[1], sStep[2]};
+          const double q[4] = {sState[0], sState[1], sState[2], sState[3]};
+          double qn[4];
+          quat_plus(q, dq, qn);
+          if (lane < 4) sCand[lane] = lane == 0 ? qn[0] : lane == 1 ? qn[1] : lane == 2 ? qn[2] : qn[3];
+          if (lane >= 3 && lane < 6) sCand[1 + lane] = sState[1 + lane] + delta;
+          if (lane >= 6 && lane < n) sCand[8 + sIdx[lane - 6]] = sState[8 + sIdx[lane - 6]] + delta;
+        }
+        wave_sync();
+        // |x|^2, |x - candidate|^2 over the variable blocks in ambient
+        // coordinates: qvec, tvec, and every parameter of a refined camera
+        double xn2 = 0.0, sn2 = 0.0;
+        const int nstate = ct > 0 ? 8 + pb->np : 7;
+        for (int m = 0; m < nstate; ++m) {
+          if (m == 7) continue;
+          const double xv = sState[m], dv = xv - sCand[m];
+          xn2 += xv * xv;
+          sn2 += dv * dv;
+        }
+        if (lane == 0) {
+          lm->consecutive_invalid = 0;
+          lm->model_cost_change = model;
+          lm->x_norm = sqrt(xn2);
+          lm->step_norm = sqrt(sn2);
+        }
+        act = kActEval;
+        break;
+      }
+      if (lane == 0) lm->action0 = act;
+    }
+    __syncthreads();
+    if (lm->action0 == kActStop) break;
+
+    // candidate cost: the second pass over the observations
+    {
+      double cost_acc = 0.0;
+      for (int i = tid; i < count; i += kPoseTB) {
+        double ox, oy, X[3];
+        src.load(i, &ox, &oy, X);
+        cost_acc += pose_obs_cost(model, sCand, a.loss_scale, ox, oy, X);
+      }
+      sCost[tid] = cost_acc;
+    }
+    __syncthreads();
+    if (wave == 0) {
+      const double cand_cost = pose_cost_total(sCost, lane);
+      const double x_cost = lm->x_cost, radius = lm->radius, df = lm->decrease_factor;
+      const double cost_change = x_cost - cand_cost;
+      const double relative_decrease = cost_change / lm->model_cost_change;
+      const bool success = isfinite(cand_cost) && relative_decrease > kMinRelativeDecrease;
+      // ParameterToleranceReached / FunctionToleranceReached: Ceres returns
+      // before accepting the candidate
+      const bool tol = lm->step_norm <= kParameterTolerance * (lm->x_norm + kParameterTolerance) ||
+                       fabs(cost_change) <= kFunctionTolerance * x_cost;
+      wave_sync();
+      if (tol) {
+        if (lane == 0) {
+          lm->n_unsuccessful += 1;
+          lm->termination = MI_BA_CONVERGENCE;
+          lm->action1 = kActStop;
+          pose_trace(a, index, lm->iteration, 1, 0, 1);
+        }
+      } else if (success) {
+        if (lane < 16) sState[lane] = sCand[lane];
+        if (lane == 0) {
+          lm->n_successful += 1;
+          lm->last_successful = 1;
+          lm->x_cost = cand_cost;
+          lm->radius = fmin(kMaxRadius, radius / fmax(1.0 / 3.0, 1.0 - pow(2.0 * relative_decrease - 1.0, 3.0)));
+          lm->decrease_factor = 2.0;
+          lm->action1 = kActAccept;
+          pose_trace(a, index, lm->iteration, 1, 1, 0);
+        }
+      } else {
+        if (lane == 0) {
+          lm->n_unsuccessful += 1;
+          lm->last_successful = 0;
+          lm->radius = radius / df;
+          lm->decrease_factor = df * 2.0;
+          lm->action1 = kActReject;
+          pose_trace(a, index, lm->iteration, 1, 0, 0);
+        }
+      }
+    }
+    __syncthreads();
+    action = lm->action1;
+    if (action == kActStop) break;
+  }
+
+  if (wave != 0) return;
+  wave_sync();
+  const int termination = lm->termination;
+  // rot_tvec_covariance: pose block of inv(J'J) at the final point (sM)
+  double cov_ok = 0.0;
+  if (a.cov && termination != MI_BA_FAILURE) {
+    if (lane < NT) {
+      for (int j = 0; j <= lane; ++j)
+        sA[lane * (NT + 1) + j] = lane < n ? sM[lane * NC + j] : (j == lane ? 1.0 : 0.0);
+      sD0[lane] = lane < n ? sM[lane * NC + lane] : 1.0;
+    }
+    if (wave_cholesky<NT>(sA, lane, kCovPivotTolerance, sD0)) {
+      cov_ok = 1.0;
+      double* cov = a.cov + (size_t)index * 36;
+#pragma unroll 1
+      for (int c = 0; c < 6; ++c) {
+        const double x = wave_chol_solve<NT>(sA, lane == c ? 1.0 : 0.0, lane, sStep);
+        if (lane < 6) cov[lane * 6 + c] = x;
+      }
+    }
+  }
+  if (lane < 16 && termination != MI_BA_FAILURE) a.state[(size_t)index * 16 + lane] = sState[lane];
+  if (lane == 0) {
+    out[0] = lm->initial_cost;
+    out[1] = lm->x_cost;
+    out[2] = lm->n_successful;
+    out[3] = lm->n_unsuccessful;
+    out[4] = termination;
+    out[5] = cov_ok;
+  }
+}
+
+struct Buf {
+  void* p = nullptr;
+  ~Buf() {
+    if (p) (void)hipFree(p);
+  }
+  template <typename T>
+  T* alloc(size_t n) {
+    if (hipMalloc(&p, n == 0 ? 8 : n * sizeof(T)) != hipSuccess) p = nullptr;
+    return static_cast<T*>(p);
+  }
+};
+
+template <int NT>
+mi_ba_status launch_pose_refine(PoseArgs a, const std::vector<PoseProblemDev>& list, Buf* buf) {
+  if (list.empty()) return MI_BA_OK;
+  int most = 0;
+  for (const PoseProblemDev& pb : list) most = pb.count > most ? pb.count : most;
+  a.lds_obs = most > kPoseLdsObs ? kPoseLdsObs : (most + 63) / 64 * 64;
+  PoseProblemDev* d = buf->alloc<PoseProblemDev>(list.size());
+  if (!d) return MI_BA_ERR_OUT_OF_MEMORY;
+  if (hipMemcpy(d, list.data(), list.size() * sizeof(PoseProblemDev), hipMemcpyHostToDevice) != hipSuccess)
+    return MI_BA_ERR_HIP;
+  a.prob = d;
+  const size_t bytes = (size_t)pose_lds_doubles<NT>(a.lds_obs) * 8;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pose_refine_kernel<NT>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+    return MI_BA_ERR_HIP;
+  hipLaunchKernelGGL(pose_refine_kernel<NT>, dim3((unsigned)list.size()), dim3(kPoseTB), bytes, 0, a);
+  return hipGetLastError() == hipSuccess ? MI_BA_OK : MI_BA_ERR_HIP;
+}
+
+}  // namespace
+}  // namespace miba
+
+using namespace miba;
+
+namespace {
+uint8_t* g_pose_trace = nullptr;
+int32_t g_pose_trace_cap = 0;
+}  // namespace
+
+extern "C" void mi_ba_pose_refine_set_trace(uint8_t* trace, int32_t capacity) {
+  g_pose_trace = capacity > 0 ? trace : nullptr;
+  g_pose_trace_cap = trace ? capacity : 0;
+}
+
+extern "C" void mi_ba_default_pose_refine_options(mi_ba_pose_refine_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  // AbsolutePoseRefinementOptions (src/estimators/pose.h:93-124)
+  o->gradient_tolerance = 1.0;
+  o->max_num_iterations = 100;
+  o->loss_function_scale = 1.0;
+  o->refine_focal_length = 1;
+  o->refine_extra_params = 1;
+  o->device = 0;
+}
+
+extern "C" int32_t mi_ba_pose_refine_intrinsics(int32_t camera_model, int32_t refine_focal_length,
+                                                int32_t refine_extra_params, int32_t* idxs) {
+  if (num_params(camera_model) < 0) return -1;
+  // the principal point stays fixed (pose.cc:251-257)
+  const unsigned mask =
+      cam_tangent_mask_all(camera_model, (refine_focal_length ? 1 : 0) | (refine_extra_params ? 4 : 0));
+  int32_t c = 0;
+  for (int k = 0; k < 8; ++k)
+    if ((mask >> k) & 1u) {
+      if (idxs) idxs[c] = k;
+      ++c;
+    }
+  return c;
+}
+
+extern "C" int32_t mi_ba_pose_refine_lds_capacity(void) { return kPoseLdsObs; }
+
+extern "C" mi_ba_status mi_ba_refine_absolute_pose_batch(const mi_ba_pose_refine_options* o,
+                                                         const mi_ba_pose_batch* b, int32_t* statuses,
+                                                         mi_ba_summary* summaries, int32_t* usable) {
+  if (!o || !b || b->num_problems < 0) return MI_BA_ERR_INVALID_ARGUMENT;
+  // AbsolutePoseRefinementOptions::Check (pose.h:119-123)
+  if (!(o->gradient_tolerance >= 0.0) || o->max_num_iterations < 0 || !(o->loss_function_scale >= 0.0))
+    return MI_BA_ERR_INVALID_ARGUMENT;
+  const int n = b->num_problems;
+  if (n == 0) return MI_BA_OK;
+  if (!statuses || !summaries || !usable || !b->obs_offsets || !b->camera_model_ids || !b->camera_param_offsets ||
+      !b->camera_params || !b->qvec || !b->tvec)
+    return MI_BA_ERR_INVALID_ARGUMENT;
+  if (b->obs_offsets[0] < 0 || b->camera_param_offsets[0] < 0) return MI_BA_ERR_INVALID_ARGUMENT;
+  for (int k = 0; k < n; ++k) {
+    const int64_t c = b->obs_offsets[k + 1] - b->obs_offsets[k];
+    if (c < 0 || c > INT32_MAX) return MI_BA_ERR_INVALID_ARGUMENT;
+    const int np = num_params(b->camera_model_ids[k]);
+    const int64_t have = b->camera_param_offsets[k + 1] - b->camera_param_offsets[k];
+    if (have < 0 || (np >= 0 && have != np)) return MI_BA_ERR_INVALID_ARGUMENT;
+  }
+  const int64_t total = b->obs_offsets[n];
+  if (total > 0 && (!b->points2D || !b->points3D)) return MI_BA_ERR_INVALID_ARGUMENT;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return MI_BA_ERR_NO_DEVICE;
+  if (o->device < 0 || o->device >= ndev) return MI_BA_ERR_INVALID_ARGUMENT;
+  if (hipSetDevice(o->device) != hipSuccess) return MI_BA_ERR_HIP;
+
+  // Host assembly: inlier compaction, unit qvec, refined-intrinsics sets.
+  std::vector<PoseProblemDev> narrow, wide;
+  std::vector<double> state(16 * (size_t)n, 0.0);
+  std::vector<double> c2, c3;  // compacted correspondences (with a mask)
+  const bool masked = b->inlier_mask != nullptr;
+  if (masked) {
+    c2.reserve(2 * (size_t)total);
+    c3.reserve(3 * (size_t)total);
+  }
+  for (int k = 0; k < n; ++k) {
+    std::memset(&summaries[k], 0, sizeof(mi_ba_summary));
+    usable[k] = 0;
+    const int model = b->camera_model_ids[k];
+    const int np = num_params(model);
+    if (np < 0) {
+      statuses[k] = MI_BA_ERR_UNSUPPORTED;
+      continue;
+    }
+    statuses[k] = MI_BA_OK;
+    PoseProblemDev pb{};
+    pb.model = model;
+    pb.np = np;
+    pb.index = k;
+    pb.ct = mi_ba_pose_refine_intrinsics(model, o->refine_focal_length, o->refine_extra_params, pb.idx);
+    const int64_t b0 = b->obs_offsets[k], b1 = b->obs_offsets[k + 1];
+    if (masked) {
+      pb.obs_begin = (int64_t)(c2.size() / 2);
+      for (int64_t i = b0; i < b1; ++i) {
+        if (!b->inlier_mask[i]) continue;
+        c2.push_back(b->points2D[2 * i]);
+        c2.push_back(b->points2D[2 * i + 1]);
+        for (int m = 0; m < 3; ++m) c3.push_back(b->points3D[3 * i + m]);
+      }
+      pb.count = (int32_t)((int64_t)(c2.size() / 2) - pb.obs_begin);
+    } else {
+      pb.obs_begin = b0;
+      pb.count = (int32_t)(b1 - b0);
+    }
+    double* st = &state[16 * (size_t)k];
+    const double* q = b->qvec + 4 * (size_t)k;
+    const double nq = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    // a unit qvec is kept bit for bit (BundleAdjuster::SetUp normalises)
+    const bool unit = quat_is_unit(q);
+    for (int m = 0; m < 4; ++m) st[m] = unit ? q[m] : q[m] / nq;
+    for (int m = 0; m < 3; ++m) st[4 + m] = b->tvec[3 * (size_t)k + m];
+    for (int m = 0; m < np; ++m) st[8 + m] = b->camera_params[b->camera_param_offsets[k] + m];
+    summaries[k].num_residuals_reduced = 2 * (int64_t)pb.count;
+    summaries[k].num_effective_parameters_reduced = pb.count > 0 ? 6 + pb.ct : 0;
+    if (pb.count == 0) {  // no residuals: nothing to do
+      summaries[k].termination_type = MI_BA_CONVERGENCE;
+      usable[k] = 1;
+      continue;
+    }
+    (pb.ct == 0 ? narrow : wide).push_back(pb);
+  }
+  if (narrow.empty() && wide.empty()) return MI_BA_OK;
+
+  const double* h2 = masked ? c2.data() : b->points2D;
+  const double* h3 = masked ? c3.data() : b->points3D;
+  const int64_t N = masked ? (int64_t)(c2.size() / 2) : total;
+  Buf bufs[8];
+  double2* d2 = bufs[0].alloc<double2>(N);
+  double* d3 = bufs[1].alloc<double>(3 * (size_t)N);
+  double* dstate = bufs[2].alloc<double>(state.size());
+  double* dout = bufs[3].alloc<double>(kOutStride * (size_t)n);
+  double* dcov = b->rot_tvec_covariance ? bufs[4].alloc<double>(36 * (size_t)n) : nullptr;
+  if (!d2 || !d3 || !dstate || !dout || (b->rot_tvec_covariance && !dcov)) return MI_BA_ERR_OUT_OF_MEMORY;
+  if (hipMemcpy(d2, h2, (size_t)N * 16, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d3, h3, (size_t)N * 24, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(dstate, state.data(), state.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(dout, 0, kOutStride * (size_t)n * 8) != hipSuccess)
+    return MI_BA_ERR_HIP;
+  PoseArgs a{};
+  a.p2 = d2;
+  a.p3 = d3;
+  a.state = dstate;
+  a.out = dout;
+  a.cov = dcov;
+  a.gradient_tolerance = o->gradient_tolerance;
+  a.loss_scale = o->loss_function_scale;
+  a.max_num_iterations = o->max_num_iterations;
+  uint8_t* const trace = g_pose_trace;
+  const int32_t trace_cap = g_pose_trace_cap;
+  if (trace) {
+    a.trace = bufs[7].alloc<uint8_t>((size_t)n * trace_cap);
+    a.trace_cap = trace_cap;
+    if (!a.trace) return MI_BA_ERR_OUT_OF_MEMORY;
+    if (hipMemset(a.trace, 0xFF, (size_t)n * trace_cap) != hipSuccess) return MI_BA_ERR_HIP;
+  }
+  // specialised on the tangent width: pose only (6) and pose + intrinsics (up to 14)
+  mi_ba_status st = launch_pose_refine<6>(a, narrow, &bufs[5]);
+  if (st != MI_BA_OK) return st;
+  st = launch_pose_refine<14>(a, wide, &bufs[6]);
+  if (st != MI_BA_OK) return st;
+  if (hipStreamSynchronize(0) != hipSuccess) return MI_BA_ERR_HIP;
+  std::vector<double> out(kOutStride * (size_t)n), cov;
+  if (hipMemcpy(state.data(), dstate, state.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(out.data(), dout, out.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
+    return MI_BA_ERR_HIP;
+  if (trace && hipMemcpy(trace, a.trace, (size_t)n * trace_cap, hipMemcpyDeviceToHost) != hipSuccess)
+    return MI_BA_ERR_HIP;
+  if (dcov) {
+    cov.resize(36 * (size_t)n);
+    if (hipMemcpy(cov.data(), dcov, cov.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return MI_BA_ERR_HIP;
+  }
+  auto finish = [&](const PoseProblemDev& pb) {
+    const int k = pb.index;
+    const double* r = &out[kOutStride * (size_t)k];
+    mi_ba_summary& s = summaries[k];
+    s.initial_cost = r[0];
+    s.final_cost = r[1];
+    s.num_successful_steps = (int32_t)r[2];
+    s.num_unsuccessful_steps = (int32_t)r[3];
+    s.termination_type = (int32_t)r[4];
+    s.num_jacobian_evaluations = 1 + s.num_successful_steps;
+    s.num_linear_solver_iterations = s.num_successful_steps + s.num_unsuccessful_steps;
+    // Ceres leaves the user's parameter blocks untouched on FAILURE
+    bool ok = s.termination_type == MI_BA_CONVERGENCE || s.termination_type == MI_BA_NO_CONVERGENCE ||
+              s.termination_type == MI_BA_USER_SUCCESS;
+    if (ok) {
+      const double* stp = &state[16 * (size_t)k];
+      for (int m = 0; m < 4; ++m) b->qvec[4 * (size_t)k + m] = stp[m];
+      for (int m = 0; m < 3; ++m) b->tvec[3 * (size_t)k + m] = stp[4 + m];
+      for (int m = 0; m < pb.ct; ++m) b->camera_params[b->camera_param_offsets[k] + pb.idx[m]] = stp[8 + pb.idx[m]];
+      if (dcov) {
+        if (r[5] != 0.0)
+          std::memcpy(b->rot_tvec_covariance + 36 * (size_t)k, &cov[36 * (size_t)k], 36 * 8);
+        else
+          ok = false;  // covariance.Compute failed (pose.cc:311-313)
+      }
+    }
+    usable[k] = ok ? 1 : 0;
+  };
+  for (const PoseProblemDev& pb : narrow) finish(pb);
+  for (const PoseProblemDev& pb : wide) finish(pb);
+  return MI_BA_OK;
+}

@@ -258,6 +258,34 @@ class RigTable(C.Structure):
     ]
 
 
+class PoseRefineOptions(C.Structure):
+    """mi_ba_pose_refine_options (AbsolutePoseRefinementOptions, estimators/pose.h)."""
+    _fields_ = [
+        ("gradient_tolerance", C.c_double),
+        ("max_num_iterations", C.c_int32),
+        ("loss_function_scale", C.c_double),
+        ("refine_focal_length", C.c_int32),
+        ("refine_extra_params", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
+class PoseBatch(C.Structure):
+    _fields_ = [
+        ("num_problems", C.c_int32),
+        ("obs_offsets", _i64p),
+        ("points2D", _dp),
+        ("points3D", _dp),
+        ("inlier_mask", _u8p),
+        ("camera_model_ids", _i32p),
+        ("camera_param_offsets", _i64p),
+        ("camera_params", _dp),
+        ("qvec", _dp),
+        ("tvec", _dp),
+        ("rot_tvec_covariance", _dp),
+    ]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [
         ("camera_model", C.c_int32),
@@ -352,6 +380,16 @@ def load(path: str = LIB_PATH):
     lib.mi_ba_rig_reduce_dense.argtypes = [C.c_int32, C.c_int32, _dp, _dp, C.POINTER(RigTable), C.c_int32, _dp, _dp]
     lib.mi_ba_rig_project_chunk.argtypes = [_i32p]
     lib.mi_ba_rig_project_chunk.restype = C.c_int32
+    lib.mi_ba_default_pose_refine_options.argtypes = [C.POINTER(PoseRefineOptions)]
+    lib.mi_ba_default_pose_refine_options.restype = None
+    lib.mi_ba_refine_absolute_pose_batch.argtypes = [C.POINTER(PoseRefineOptions), C.POINTER(PoseBatch), _i32p,
+                                                     C.c_void_p, _i32p]
+    lib.mi_ba_pose_refine_intrinsics.argtypes = [C.c_int32, C.c_int32, C.c_int32, _i32p]
+    lib.mi_ba_pose_refine_intrinsics.restype = C.c_int32
+    lib.mi_ba_pose_refine_set_trace.argtypes = [_u8p, C.c_int32]
+    lib.mi_ba_pose_refine_set_trace.restype = None
+    lib.mi_ba_pose_refine_lds_capacity.argtypes = []
+    lib.mi_ba_pose_refine_lds_capacity.restype = C.c_int32
     _lib = lib
     return lib
 
@@ -899,6 +937,138 @@ def solve_batch(options, scenes, semantics=None, max_concurrent: int = 8):
           "mi_ba_solve_batch")
     del keep
     return list(st), list(sums)
+
+
+def default_pose_refine_options(**kw) -> PoseRefineOptions:
+    o = PoseRefineOptions()
+    load().mi_ba_default_pose_refine_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def pose_refine_intrinsics(model: int, refine_focal_length: bool = True, refine_extra_params: bool = True):
+    """Parameter indices RefineAbsolutePose refines for a model (the principal
+    point never); None for an unsupported model."""
+    idx = np.zeros(8, np.int32)
+    n = load().mi_ba_pose_refine_intrinsics(int(model), int(bool(refine_focal_length)), int(bool(refine_extra_params)),
+                                            idx.ctypes.data_as(_i32p))
+    return None if n < 0 else idx[:n].copy()
+
+
+def pose_refine_lds_capacity() -> int:
+    return int(load().mi_ba_pose_refine_lds_capacity())
+
+
+@dataclass
+class PoseProblem:
+    """One RefineAbsolutePose problem (estimators/pose.h:185-198)."""
+    camera_model: int
+    camera_params: np.ndarray            # [np]
+    qvec: np.ndarray                     # [4]
+    tvec: np.ndarray                     # [3]
+    points2D: np.ndarray                 # [N][2]
+    points3D: np.ndarray                 # [N][3]
+    inlier_mask: Optional[np.ndarray] = None  # [N], nonzero = inlier (None: all)
+
+    def copy(self) -> "PoseProblem":
+        return PoseProblem(self.camera_model, self.camera_params.copy(), self.qvec.copy(), self.tvec.copy(),
+                           self.points2D.copy(), self.points3D.copy(),
+                           None if self.inlier_mask is None else self.inlier_mask.copy())
+
+
+@dataclass
+class PoseBatchResult:
+    statuses: np.ndarray                 # [n] mi_ba_status per problem
+    summaries: list                      # [n] Summary
+    usable: np.ndarray                   # [n] 0 / 1
+    qvec: np.ndarray                     # [n][4]
+    tvec: np.ndarray                     # [n][3]
+    camera_params: list                  # [n] arrays
+    covariance: Optional[np.ndarray]     # [n][6][6] (rotation tangent, translation) or None
+
+
+def refine_absolute_pose_batch(options: PoseRefineOptions, problems, covariance=False,
+                               trace: Optional[np.ndarray] = None) -> PoseBatchResult:
+    """mi_ba_refine_absolute_pose_batch: every problem of the list in one
+    launch.  The problems are not modified; the refined parameters come back
+    in the result.  covariance: True, or an [n][6][6] array whose rows of
+    problems without a covariance are left as given.  trace: a uint8 array
+    [n][cap] that receives the LM trace (mi_ba_pose_refine_set_trace)."""
+    n = len(problems)
+    if trace is not None:
+        assert trace.dtype == np.uint8 and trace.flags.c_contiguous and trace.shape[0] == n
+    counts = [int(np.asarray(p.points2D).reshape(-1, 2).shape[0]) for p in problems]
+    for p, c in zip(problems, counts):
+        if np.asarray(p.points3D).reshape(-1, 3).shape[0] != c:
+            raise ValueError("points2D and points3D differ in length")
+        if p.inlier_mask is not None and len(p.inlier_mask) != c:
+            raise ValueError("inlier_mask and points2D differ in length")
+    obs_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    cat = lambda xs, w: (np.ascontiguousarray(np.concatenate([np.asarray(x, np.float64).reshape(-1, w) for x in xs]))
+                         if n else np.zeros((0, w)))
+    p2, p3 = cat([p.points2D for p in problems], 2), cat([p.points3D for p in problems], 3)
+    mask = None
+    if any(p.inlier_mask is not None for p in problems):
+        mask = np.ascontiguousarray(np.concatenate(
+            [np.ones(c, np.uint8) if p.inlier_mask is None else (np.asarray(p.inlier_mask) != 0).astype(np.uint8)
+             for p, c in zip(problems, counts)]))
+    models = np.array([p.camera_model for p in problems], np.int32)
+    cam_off = np.concatenate([[0], np.cumsum([len(p.camera_params) for p in problems])]).astype(np.int64)
+    cams = np.ascontiguousarray(np.concatenate([np.asarray(p.camera_params, np.float64) for p in problems])
+                                if n else np.zeros(0))
+    q = np.ascontiguousarray(np.array([p.qvec for p in problems], np.float64).reshape(n, 4))
+    t = np.ascontiguousarray(np.array([p.tvec for p in problems], np.float64).reshape(n, 3))
+    cov = None
+    if covariance is True:
+        cov = np.zeros((n, 6, 6))
+    elif covariance is not False and covariance is not None:
+        cov = np.ascontiguousarray(covariance, dtype=np.float64).reshape(n, 6, 6).copy()
+    b = PoseBatch()
+    b.num_problems = n
+    b.obs_offsets = _ptr(obs_off, _i64p)
+    b.points2D = _ptr(p2, _dp)
+    b.points3D = _ptr(p3, _dp)
+    b.inlier_mask = _ptr(mask, _u8p)
+    b.camera_model_ids = _ptr(models, _i32p)
+    b.camera_param_offsets = _ptr(cam_off, _i64p)
+    b.camera_params = _ptr(cams, _dp)
+    b.qvec = _ptr(q, _dp)
+    b.tvec = _ptr(t, _dp)
+    b.rot_tvec_covariance = _ptr(cov, _dp)
+    st = np.zeros(n, np.int32)
+    us = np.zeros(n, np.int32)
+    sums = (Summary * max(n, 1))()
+    if trace is not None:
+        load().mi_ba_pose_refine_set_trace(_ptr(trace, _u8p), int(trace.shape[1]))
+    try:
+        rc = load().mi_ba_refine_absolute_pose_batch(C.byref(options), C.byref(b), _ptr(st, _i32p),
+                                                     C.cast(sums, C.c_void_p), _ptr(us, _i32p))
+    finally:
+        if trace is not None:
+            load().mi_ba_pose_refine_set_trace(None, 0)
+    check(rc, "mi_ba_refine_absolute_pose_batch")
+    return PoseBatchResult(st, list(sums)[:n], us, q, t, [cams[cam_off[k]:cam_off[k + 1]].copy() for k in range(n)], cov)
+
+
+def refine_absolute_pose(options: PoseRefineOptions, problem: PoseProblem, covariance=False) -> PoseBatchResult:
+    """RefineAbsolutePose of one problem (a batch of one)."""
+    return refine_absolute_pose_batch(options, [problem], covariance)
+
+
+def pose_problem_scene(problem: PoseProblem) -> Scene:
+    """The equivalent bundle-adjustment scene of a pose problem: one image,
+    one camera, every inlier a constant point (AddConstantPoint)."""
+    keep = slice(None) if problem.inlier_mask is None else np.asarray(problem.inlier_mask) != 0
+    p2 = np.asarray(problem.points2D, np.float64).reshape(-1, 2)[keep]
+    p3 = np.asarray(problem.points3D, np.float64).reshape(-1, 3)[keep]
+    m = len(p2)
+    return Scene(int(problem.camera_model), np.asarray(problem.camera_params, np.float64).reshape(1, -1).copy(),
+                 np.asarray(problem.qvec, np.float64).reshape(1, 4).copy(),
+                 np.asarray(problem.tvec, np.float64).reshape(1, 3).copy(), np.zeros(1, np.int32), p3.copy(), p2.copy(),
+                 np.zeros(m, np.int32), np.arange(m, dtype=np.int32), point_config=np.full(m, 2, np.uint8))
 
 
 def squared_reprojection_errors(scene: Scene, device: int = 0) -> np.ndarray:
