@@ -9,6 +9,10 @@
 // Where the reference CHECKs (options, the two size checks), this throws
 // std::invalid_argument; device errors throw std::runtime_error.
 //
+// RefineGeneralizedAbsolutePose (estimators/pose.h:221-233; pose.cc:354-520),
+// the pose of a camera rig from the correspondences of several of its cameras,
+// follows below on mi_ba_refine_generalized_absolute_pose_batch.
+//
 // Differences to the reference: a qvec that is not of unit length is
 // normalised first; the linear solve is a Cholesky of the normal equations,
 // not DENSE_QR.
@@ -174,6 +178,179 @@ inline bool RefineAbsolutePose(const AbsolutePoseRefinementOptions& options, con
   p.camera = camera;
   p.rot_tvec_covariance = rot_tvec_covariance;
   return RefineAbsolutePoses(options, {p})[0];
+}
+
+// One problem of RefineGeneralizedAbsolutePoses: the arguments of
+// RefineGeneralizedAbsolutePose (estimators/pose.h:221-233).  camera_idxs[i]
+// is the rig camera of correspondence i; rig_qvecs / rig_tvecs are the
+// cameras' constant poses relative to the rig, qvec / tvec the rig pose.
+// Differences to the reference: qvec and every rig_qvec that is not of unit
+// length are normalised first.
+struct GeneralizedAbsolutePoseProblem {
+  const std::vector<char>* inlier_mask = nullptr;
+  const std::vector<std::array<double, 2>>* points2D = nullptr;
+  const std::vector<std::array<double, 3>>* points3D = nullptr;
+  const std::vector<size_t>* camera_idxs = nullptr;
+  const std::vector<std::array<double, 4>>* rig_qvecs = nullptr;
+  const std::vector<std::array<double, 3>>* rig_tvecs = nullptr;
+  std::array<double, 4>* qvec = nullptr;
+  std::array<double, 3>* tvec = nullptr;
+  std::vector<Camera>* cameras = nullptr;
+  std::array<double, 36>* rot_tvec_covariance = nullptr;
+};
+
+// Refines every rig problem in one call (mi_ba_refine_generalized_absolute_
+// pose_batch); returns per problem whether the solution is usable.  The
+// reference's seven CHECKs throw std::invalid_argument, an unknown camera
+// model std::domain_error, a rig beyond mi_ba_generalized_pose_limits and
+// device errors std::runtime_error.
+inline std::vector<bool> RefineGeneralizedAbsolutePoses(const AbsolutePoseRefinementOptions& options,
+                                                        const std::vector<GeneralizedAbsolutePoseProblem>& problems,
+                                                        std::vector<SolverSummary>* summaries = nullptr) {
+  const int n = (int)problems.size();
+  std::vector<int64_t> obs_off(n + 1, 0), cam_off(n + 1, 0), prm_off(1, 0);
+  bool any_cov = false;
+  for (int k = 0; k < n; ++k) {
+    const GeneralizedAbsolutePoseProblem& p = problems[k];
+    if (!p.inlier_mask || !p.points2D || !p.points3D || !p.camera_idxs || !p.rig_qvecs || !p.rig_tvecs || !p.qvec ||
+        !p.tvec || !p.cameras)
+      throw std::invalid_argument("RefineGeneralizedAbsolutePose: null argument");
+    // pose.cc:364-371
+    if (p.points2D->size() != p.inlier_mask->size()) throw std::invalid_argument("points2D.size() != inlier_mask.size()");
+    if (p.points2D->size() != p.points3D->size()) throw std::invalid_argument("points2D.size() != points3D.size()");
+    if (p.points2D->size() != p.camera_idxs->size()) throw std::invalid_argument("points2D.size() != camera_idxs.size()");
+    if (p.rig_qvecs->size() != p.rig_tvecs->size()) throw std::invalid_argument("rig_qvecs.size() != rig_tvecs.size()");
+    if (p.rig_qvecs->size() != p.cameras->size()) throw std::invalid_argument("rig_qvecs.size() != cameras->size()");
+    // CHECK_GE(min camera_idxs, 0) holds for size_t; CHECK_LT(max camera_idxs, cameras->size())
+    for (size_t ci : *p.camera_idxs)
+      if (ci >= p.cameras->size()) throw std::invalid_argument("camera_idxs out of range");
+    obs_off[k + 1] = obs_off[k] + (int64_t)p.points2D->size();
+    cam_off[k + 1] = cam_off[k] + (int64_t)p.cameras->size();
+    for (const Camera& c : *p.cameras) prm_off.push_back(prm_off.back() + (int64_t)c.params.size());
+    any_cov = any_cov || p.rot_tvec_covariance;
+  }
+  options.Check();
+  if (summaries) summaries->assign(n, SolverSummary());
+  std::vector<bool> usable(n, false);
+  if (n == 0) return usable;
+  const size_t N = (size_t)obs_off[n], NC = (size_t)cam_off[n];
+  std::vector<double> p2(2 * N), p3(3 * N), cams((size_t)prm_off.back()), rq(4 * NC), rt(3 * NC), q(4 * (size_t)n),
+      t(3 * (size_t)n), cov(any_cov ? 36 * (size_t)n : 0);
+  std::vector<uint8_t> mask(N);
+  std::vector<int32_t> cidx(N), models(NC);
+  for (int k = 0; k < n; ++k) {
+    const GeneralizedAbsolutePoseProblem& p = problems[k];
+    for (size_t i = 0; i < p.points2D->size(); ++i) {
+      const size_t o = (size_t)obs_off[k] + i;
+      p2[2 * o] = (*p.points2D)[i][0];
+      p2[2 * o + 1] = (*p.points2D)[i][1];
+      for (int m = 0; m < 3; ++m) p3[3 * o + m] = (*p.points3D)[i][m];
+      mask[o] = (*p.inlier_mask)[i] ? 1 : 0;
+      cidx[o] = (int32_t)(*p.camera_idxs)[i];
+    }
+    for (size_t c = 0; c < p.cameras->size(); ++c) {
+      const size_t g = (size_t)cam_off[k] + c;
+      const Camera& cam = (*p.cameras)[c];
+      models[g] = cam.model_id;
+      for (size_t m = 0; m < cam.params.size(); ++m) cams[(size_t)prm_off[g] + m] = cam.params[m];
+      for (int m = 0; m < 4; ++m) rq[4 * g + m] = (*p.rig_qvecs)[c][m];
+      for (int m = 0; m < 3; ++m) rt[3 * g + m] = (*p.rig_tvecs)[c][m];
+    }
+    for (int m = 0; m < 4; ++m) q[4 * (size_t)k + m] = (*p.qvec)[m];
+    for (int m = 0; m < 3; ++m) t[3 * (size_t)k + m] = (*p.tvec)[m];
+  }
+  mi_ba_pose_refine_options o;
+  mi_ba_default_pose_refine_options(&o);
+  o.gradient_tolerance = options.gradient_tolerance;
+  o.max_num_iterations = options.max_num_iterations;
+  o.loss_function_scale = options.loss_function_scale;
+  o.refine_focal_length = options.refine_focal_length ? 1 : 0;
+  o.refine_extra_params = options.refine_extra_params ? 1 : 0;
+  o.device = options.device;
+  mi_ba_generalized_pose_batch b{};
+  b.num_problems = n;
+  b.obs_offsets = obs_off.data();
+  b.points2D = p2.data();
+  b.points3D = p3.data();
+  b.inlier_mask = mask.data();
+  b.camera_idxs = cidx.data();
+  b.camera_offsets = cam_off.data();
+  b.camera_model_ids = models.data();
+  b.camera_param_offsets = prm_off.data();
+  b.camera_params = cams.data();
+  b.rig_qvecs = rq.data();
+  b.rig_tvecs = rt.data();
+  b.qvec = q.data();
+  b.tvec = t.data();
+  b.rot_tvec_covariance = any_cov ? cov.data() : nullptr;
+  std::vector<int32_t> statuses(n), ok(n);
+  std::vector<mi_ba_summary> sums(n);
+  const mi_ba_status st = mi_ba_refine_generalized_absolute_pose_batch(&o, &b, statuses.data(), sums.data(), ok.data());
+  if (st == MI_BA_ERR_INVALID_ARGUMENT) throw std::invalid_argument("RefineGeneralizedAbsolutePose: invalid argument");
+  if (st != MI_BA_OK) throw std::runtime_error(std::string("RefineGeneralizedAbsolutePose: ") + mi_ba_status_string(st));
+  for (int k = 0; k < n; ++k) {
+    const GeneralizedAbsolutePoseProblem& p = problems[k];
+    if (statuses[k] == MI_BA_ERR_UNSUPPORTED) {
+      // camera_models.h:140-141 throws for an unknown model (one with inliers)
+      for (size_t i = 0; i < p.camera_idxs->size(); ++i)
+        if ((*p.inlier_mask)[i] && mi_ba_num_params((*p.cameras)[(*p.camera_idxs)[i]].model_id) < 0)
+          throw std::domain_error("Camera model does not exist");
+      throw std::runtime_error("RefineGeneralizedAbsolutePose: the rig exceeds mi_ba_generalized_pose_limits");
+    }
+    if (statuses[k] != MI_BA_OK)
+      throw std::runtime_error(std::string("RefineGeneralizedAbsolutePose: ") + mi_ba_status_string(statuses[k]));
+    SolverSummary s;
+    s.num_residuals_reduced = sums[k].num_residuals_reduced;
+    s.num_effective_parameters_reduced = sums[k].num_effective_parameters_reduced;
+    s.num_successful_steps = sums[k].num_successful_steps;
+    s.num_unsuccessful_steps = sums[k].num_unsuccessful_steps;
+    s.termination_type = (SolverSummary::TerminationType)sums[k].termination_type;
+    s.initial_cost = sums[k].initial_cost;
+    s.final_cost = sums[k].final_cost;
+    s.num_jacobian_evaluations = sums[k].num_jacobian_evaluations;
+    s.num_linear_solver_iterations = sums[k].num_linear_solver_iterations;
+    if (summaries) (*summaries)[k] = s;
+    // the library writes parameters back only where Ceres would
+    for (int m = 0; m < 4; ++m) (*p.qvec)[m] = q[4 * (size_t)k + m];
+    for (int m = 0; m < 3; ++m) (*p.tvec)[m] = t[3 * (size_t)k + m];
+    for (size_t c = 0; c < p.cameras->size(); ++c) {
+      Camera& cam = (*p.cameras)[c];
+      for (size_t m = 0; m < cam.params.size(); ++m) cam.params[m] = cams[(size_t)prm_off[(size_t)cam_off[k] + c] + m];
+    }
+    if (p.rot_tvec_covariance && ok[k])
+      for (int m = 0; m < 36; ++m) (*p.rot_tvec_covariance)[m] = cov[36 * (size_t)k + m];
+    usable[k] = ok[k] != 0;
+    if (options.print_summary) {
+      PrintHeading2("Pose refinement report");
+      PrintSolverSummary(s);
+    }
+  }
+  return usable;
+}
+
+// RefineGeneralizedAbsolutePose (pose.cc:354-520), the reference's argument order.
+inline bool RefineGeneralizedAbsolutePose(const AbsolutePoseRefinementOptions& options,
+                                          const std::vector<char>& inlier_mask,
+                                          const std::vector<std::array<double, 2>>& points2D,
+                                          const std::vector<std::array<double, 3>>& points3D,
+                                          const std::vector<size_t>& camera_idxs,
+                                          const std::vector<std::array<double, 4>>& rig_qvecs,
+                                          const std::vector<std::array<double, 3>>& rig_tvecs,
+                                          std::array<double, 4>* qvec, std::array<double, 3>* tvec,
+                                          std::vector<Camera>* cameras,
+                                          std::array<double, 36>* rot_tvec_covariance = nullptr) {
+  GeneralizedAbsolutePoseProblem p;
+  p.inlier_mask = &inlier_mask;
+  p.points2D = &points2D;
+  p.points3D = &points3D;
+  p.camera_idxs = &camera_idxs;
+  p.rig_qvecs = &rig_qvecs;
+  p.rig_tvecs = &rig_tvecs;
+  p.qvec = qvec;
+  p.tvec = tvec;
+  p.cameras = cameras;
+  p.rot_tvec_covariance = rot_tvec_covariance;
+  return RefineGeneralizedAbsolutePoses(options, {p})[0];
 }
 
 }  // namespace colmap_amd

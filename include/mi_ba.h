@@ -860,6 +860,79 @@ int32_t mi_ba_pose_refine_lds_capacity(void);
  * NULL switches it off.  Process-wide: not for concurrent callers. */
 void mi_ba_pose_refine_set_trace(uint8_t* trace, int32_t capacity);
 
+/* --- batched generalized absolute-pose refinement (camera rigs) ------------
+ * Additive entry points (MI_BA_ABI_VERSION stays 4).
+ * RefineGeneralizedAbsolutePose (src/estimators/pose.cc:354-520): the pose of
+ * a whole rig from the 2D-3D correspondences of several of its cameras.  The
+ * residual is RigBundleAdjustmentCostFunction's (cost_functions.h:160-214):
+ * q = q_rel * q_rig, t = R(q_rel) t_rig + t_rel, every point and every
+ * relative pose constant, CauchyLoss(loss_function_scale).  The rig pose
+ * lives on QuaternionManifold x R^3.  A camera without an inlier is not in the
+ * problem (pose.cc:424): its parameters come back bit for bit and it adds
+ * nothing to the tangent.  A camera with inliers refines
+ * mi_ba_pose_refine_intrinsics(model, flags) (the principal point never).
+ * Options, solver defaults, the linear solve (Cholesky of the normal
+ * equations), statuses, usable, summaries, covariance rule and trace are
+ * those of mi_ba_refine_absolute_pose_batch above;
+ * num_effective_parameters_reduced is 6 + the refined intrinsics of the
+ * cameras with inliers.
+ *
+ * Problem k owns the correspondences obs_offsets[k] .. obs_offsets[k + 1) and
+ * the rig cameras camera_offsets[k] .. camera_offsets[k + 1); camera c (an
+ * index into the camera arrays) owns the parameters camera_param_offsets[c] ..
+ * camera_param_offsets[c + 1).  camera_idxs[i] is the camera of
+ * correspondence i, local to its problem's rig.  qvec and every rig_qvec that
+ * is not of unit length are normalised first (the reference does not). */
+typedef struct mi_ba_generalized_pose_batch {
+  int32_t num_problems;
+  const int64_t* obs_offsets;          /* [num_problems + 1] */
+  const double* points2D;              /* [obs_offsets[n]][2] */
+  const double* points3D;              /* [obs_offsets[n]][3] */
+  const uint8_t* inlier_mask;          /* nullable (= all inliers); nonzero = used */
+  const int32_t* camera_idxs;          /* [obs_offsets[n]] camera of the correspondence, 0 .. rig size) */
+  const int64_t* camera_offsets;       /* [num_problems + 1] */
+  const int32_t* camera_model_ids;     /* [camera_offsets[n]] MI_BA_* model id */
+  const int64_t* camera_param_offsets; /* [camera_offsets[n] + 1] */
+  double* camera_params;               /* (in/out) */
+  const double* rig_qvecs;             /* [camera_offsets[n]][4] relative pose of the camera in its rig */
+  const double* rig_tvecs;             /* [camera_offsets[n]][3] */
+  double* qvec;                        /* (in/out) [num_problems][4] rig pose (w,x,y,z) */
+  double* tvec;                        /* (in/out) [num_problems][3] */
+  double* rot_tvec_covariance;         /* nullable (out) [num_problems][36] row-major 6 x 6 */
+} mi_ba_generalized_pose_batch;
+
+/* Solves every problem of the batch; see mi_ba_refine_absolute_pose_batch for
+ * statuses / summaries / usable.  statuses[k] is MI_BA_ERR_UNSUPPORTED (the
+ * problem is skipped, its neighbours are unaffected) for a rig that uses a
+ * model outside the nine supported (FULL_OPENCV, THIN_PRISM_FISHEYE) on a
+ * camera with inliers, or that exceeds mi_ba_generalized_pose_limits.
+ * The call returns MI_BA_ERR_INVALID_ARGUMENT, before any device is touched,
+ * where the reference CHECKs: a camera_idxs value outside its rig (outliers
+ * included), negative counts, offsets that decrease, a camera whose parameter
+ * count does not fit its model, options failing Check().
+ * rot_tvec_covariance is the rig-pose block of inv(J'J) over the full tangent
+ * (rig pose and every refined intrinsic).  Every sum runs in a fixed order
+ * without atomics: the same problem gives the same bits on every run, at
+ * every position of a batch, and under any permutation of its correspondences
+ * that keeps each camera's own order. */
+mi_ba_status mi_ba_refine_generalized_absolute_pose_batch(const mi_ba_pose_refine_options* options,
+                                                          const mi_ba_generalized_pose_batch* batch,
+                                                          int32_t* statuses, mi_ba_summary* summaries,
+                                                          int32_t* usable);
+
+/* The kernel's limits: cameras per rig, tangent size (6 + refined intrinsics
+ * of the cameras with inliers) and the inlier correspondences of one problem
+ * kept resident in LDS (more stream from device memory).  Host only. */
+void mi_ba_generalized_pose_limits(int32_t* max_cameras, int32_t* max_tangent, int32_t* lds_capacity);
+
+/* The argument checks and the per-problem plan of the solve, without a
+ * device: statuses[k] as the solve returns it, tangent_sizes[k] (0 for a
+ * problem without inliers, -1 with an unsupported model on a used camera) and
+ * inlier_counts[k].  Outputs are nullable.  Host only. */
+mi_ba_status mi_ba_generalized_pose_plan(const mi_ba_pose_refine_options* options,
+                                         const mi_ba_generalized_pose_batch* batch, int32_t* statuses,
+                                         int32_t* tangent_sizes, int64_t* inlier_counts);
+
 /* Per-kernel HIP-event timing on the context's stream (enabled with
  * mi_ba_set_timing).  name: "reproj_jacobian", "semantic_jacobian", ... */
 mi_ba_status mi_ba_set_timing(mi_ba_context* ctx, int32_t enabled);

@@ -37,30 +37,15 @@
 
 #include "../../include/mi_ba.h"
 #include "ba_math.h"
+#include "pose_common.h"
 #include "reproj_block.h"
 
 namespace miba {
 namespace {
 
-constexpr int kPoseTB = 256;
-constexpr int kPoseWaves = kPoseTB / 64;
 // Most observations kept in LDS (5 doubles each: 80 KiB of the CU's 160 KiB,
 // beside 70 KiB of slabs and system at the 14-wide instantiation).
 constexpr int kPoseLdsObs = 2048;
-constexpr int kColStride = 129;
-
-// Ceres defaults RefineAbsolutePose leaves alone (solver.h).
-constexpr double kFunctionTolerance = 1e-6;
-constexpr double kParameterTolerance = 1e-8;
-constexpr int kMaxConsecutiveInvalid = 5;
-constexpr double kInitialRadius = 1e4;
-constexpr double kMinRelativeDecrease = 1e-3;
-constexpr double kMinRadius = 1e-32;
-constexpr double kMaxRadius = 1e16;
-// covariance: a pivot at or below this fraction of the column's own diagonal
-// entry is rank deficiency
-constexpr double kCovPivotTolerance = 1e-14;
-
 struct PoseProblemDev {
   int64_t obs_begin;  // into the compacted correspondence arrays
   int32_t count;      // inliers
@@ -71,8 +56,6 @@ struct PoseProblemDev {
   int32_t index;      // problem index of the batch (state / out / cov rows)
   int32_t pad;
 };
-
-constexpr int kOutStride = 8;  // initial cost, final cost, successful, unsuccessful, termination, covariance ok
 
 struct PoseArgs {
   const PoseProblemDev* prob;
@@ -89,26 +72,11 @@ struct PoseArgs {
   int32_t trace_cap;
 };
 
-enum { kActStop = 0, kActEval = 1, kActAccept = 2, kActReject = 3 };
-
 // trace byte of iteration it (1-based): bit 0 step valid, bit 1 successful,
 // bit 2 the iteration ended the solve
 __device__ __forceinline__ void pose_trace(const PoseArgs& a, int index, int it, int valid, int successful, int end) {
   if (a.trace && it >= 1 && it <= a.trace_cap)
     a.trace[(size_t)index * a.trace_cap + it - 1] = (uint8_t)(valid | successful << 1 | end << 2);
-}
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// xor tree: the same order on every run
-__device__ __forceinline__ double wave_sum_fixed(double v) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 struct PoseObsSource {
@@ -208,14 +176,6 @@ __device__ inline void pose_obs_rows(int model, const double* st, const int* idx
   J1[NT] = r1 * sc;
 }
 
-// Total of the per-thread costs in sCost (wave 0; every lane gets the sum).
-__device__ inline double pose_cost_total(const double* sCost, int lane) {
-  double c = sCost[lane];
-#pragma unroll
-  for (int w = 1; w < kPoseWaves; ++w) c += sCost[64 * w + lane];
-  return wave_sum_fixed(c);
-}
-
 // Dense Cholesky by one wave, in LDS: lane i < NT owns row i of the lower
 // triangle in sA (row stride NT + 1: the lanes' rows start on distinct even
 // banks); on return sA holds L.  A pivot k with !(pivot > tol * d0[k]) makes
@@ -267,15 +227,6 @@ __device__ inline double wave_chol_solve(const double* sA, double b, int lane, d
   wave_sync();
   return b;
 }
-
-// LM state of one problem, in LDS: read and written by wave 0 only, so no
-// register holds it across the observation passes.
-struct PoseLm {
-  double x_cost, initial_cost, radius, decrease_factor;
-  double model_cost_change, x_norm, step_norm, pad;
-  int iteration, consecutive_invalid, n_successful, n_unsuccessful;
-  int termination, last_successful, action0, action1;
-};
 
 template <int NT>
 constexpr int pose_lds_doubles(int lds_obs) {
@@ -639,18 +590,6 @@ __global__ __launch_bounds__(kPoseTB) void pose_refine_kernel(PoseArgs a) {
   }
 }
 
-struct Buf {
-  void* p = nullptr;
-  ~Buf() {
-    if (p) (void)hipFree(p);
-  }
-  template <typename T>
-  T* alloc(size_t n) {
-    if (hipMalloc(&p, n == 0 ? 8 : n * sizeof(T)) != hipSuccess) p = nullptr;
-    return static_cast<T*>(p);
-  }
-};
-
 template <int NT>
 mi_ba_status launch_pose_refine(PoseArgs a, const std::vector<PoseProblemDev>& list, Buf* buf) {
   if (list.empty()) return MI_BA_OK;
@@ -679,6 +618,11 @@ namespace {
 uint8_t* g_pose_trace = nullptr;
 int32_t g_pose_trace_cap = 0;
 }  // namespace
+
+void miba::pose_trace_target(uint8_t** trace, int32_t* capacity) {
+  *trace = g_pose_trace;
+  *capacity = g_pose_trace_cap;
+}
 
 extern "C" void mi_ba_pose_refine_set_trace(uint8_t* trace, int32_t capacity) {
   g_pose_trace = capacity > 0 ? trace : nullptr;

@@ -286,6 +286,26 @@ class PoseBatch(C.Structure):
     ]
 
 
+class GeneralizedPoseBatch(C.Structure):
+    _fields_ = [
+        ("num_problems", C.c_int32),
+        ("obs_offsets", _i64p),
+        ("points2D", _dp),
+        ("points3D", _dp),
+        ("inlier_mask", _u8p),
+        ("camera_idxs", _i32p),
+        ("camera_offsets", _i64p),
+        ("camera_model_ids", _i32p),
+        ("camera_param_offsets", _i64p),
+        ("camera_params", _dp),
+        ("rig_qvecs", _dp),
+        ("rig_tvecs", _dp),
+        ("qvec", _dp),
+        ("tvec", _dp),
+        ("rot_tvec_covariance", _dp),
+    ]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [
         ("camera_model", C.c_int32),
@@ -388,6 +408,13 @@ def load(path: str = LIB_PATH):
     lib.mi_ba_pose_refine_intrinsics.restype = C.c_int32
     lib.mi_ba_pose_refine_set_trace.argtypes = [_u8p, C.c_int32]
     lib.mi_ba_pose_refine_set_trace.restype = None
+    lib.mi_ba_refine_generalized_absolute_pose_batch.argtypes = [C.POINTER(PoseRefineOptions),
+                                                                 C.POINTER(GeneralizedPoseBatch), _i32p, C.c_void_p,
+                                                                 _i32p]
+    lib.mi_ba_generalized_pose_limits.argtypes = [_i32p, _i32p, _i32p]
+    lib.mi_ba_generalized_pose_limits.restype = None
+    lib.mi_ba_generalized_pose_plan.argtypes = [C.POINTER(PoseRefineOptions), C.POINTER(GeneralizedPoseBatch), _i32p,
+                                                _i32p, _i64p]
     lib.mi_ba_pose_refine_lds_capacity.argtypes = []
     lib.mi_ba_pose_refine_lds_capacity.restype = C.c_int32
     _lib = lib
@@ -1056,6 +1083,137 @@ def refine_absolute_pose_batch(options: PoseRefineOptions, problems, covariance=
 def refine_absolute_pose(options: PoseRefineOptions, problem: PoseProblem, covariance=False) -> PoseBatchResult:
     """RefineAbsolutePose of one problem (a batch of one)."""
     return refine_absolute_pose_batch(options, [problem], covariance)
+
+
+@dataclass
+class GeneralizedPoseProblem:
+    """One RefineGeneralizedAbsolutePose problem (estimators/pose.h:221-233):
+    a rig of cameras with constant relative poses, correspondences tagged
+    with their camera, and the rig pose."""
+    camera_models: list                  # [C] model ids
+    camera_params: list                  # [C] arrays
+    rig_qvecs: np.ndarray                # [C][4]
+    rig_tvecs: np.ndarray                # [C][3]
+    qvec: np.ndarray                     # [4]
+    tvec: np.ndarray                     # [3]
+    points2D: np.ndarray                 # [N][2]
+    points3D: np.ndarray                 # [N][3]
+    camera_idxs: np.ndarray              # [N] camera of the correspondence
+    inlier_mask: Optional[np.ndarray] = None  # [N], nonzero = inlier (None: all)
+
+    def copy(self) -> "GeneralizedPoseProblem":
+        return GeneralizedPoseProblem(list(self.camera_models), [np.array(p, np.float64) for p in self.camera_params],
+                                      np.array(self.rig_qvecs, np.float64), np.array(self.rig_tvecs, np.float64),
+                                      np.array(self.qvec, np.float64), np.array(self.tvec, np.float64),
+                                      np.array(self.points2D, np.float64), np.array(self.points3D, np.float64),
+                                      np.array(self.camera_idxs),
+                                      None if self.inlier_mask is None else np.array(self.inlier_mask))
+
+
+class _GeneralizedPoseArrays:
+    """The struct of arrays of a list of GeneralizedPoseProblem (kept alive
+    beside the ctypes struct that points into it)."""
+
+    def __init__(self, problems, covariance=False):
+        n = self.n = len(problems)
+        counts = [int(np.asarray(p.points2D).reshape(-1, 2).shape[0]) for p in problems]
+        for p, c in zip(problems, counts):
+            if np.asarray(p.points3D).reshape(-1, 3).shape[0] != c:
+                raise ValueError("points2D and points3D differ in length")
+            if len(np.asarray(p.camera_idxs).reshape(-1)) != c:
+                raise ValueError("camera_idxs and points2D differ in length")
+            if p.inlier_mask is not None and len(p.inlier_mask) != c:
+                raise ValueError("inlier_mask and points2D differ in length")
+            nc = len(p.camera_models)
+            if len(p.camera_params) != nc or np.asarray(p.rig_qvecs).reshape(-1, 4).shape[0] != nc or \
+                    np.asarray(p.rig_tvecs).reshape(-1, 3).shape[0] != nc:
+                raise ValueError("cameras, rig_qvecs and rig_tvecs differ in length")
+        cat = lambda xs, w, dt=np.float64: (np.ascontiguousarray(
+            np.concatenate([np.asarray(x, dt).reshape(-1, w) for x in xs])) if n else np.zeros((0, w), dt))
+        self.obs_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        self.p2, self.p3 = cat([p.points2D for p in problems], 2), cat([p.points3D for p in problems], 3)
+        self.cidx = cat([p.camera_idxs for p in problems], 1, np.int32).reshape(-1)
+        self.mask = None
+        if any(p.inlier_mask is not None for p in problems):
+            self.mask = np.ascontiguousarray(np.concatenate(
+                [np.ones(c, np.uint8) if p.inlier_mask is None else (np.asarray(p.inlier_mask) != 0).astype(np.uint8)
+                 for p, c in zip(problems, counts)]))
+        self.cam_off = np.concatenate([[0], np.cumsum([len(p.camera_models) for p in problems])]).astype(np.int64)
+        self.models = np.array([m for p in problems for m in p.camera_models], np.int32)
+        plens = [len(c) for p in problems for c in p.camera_params]
+        self.prm_off = np.concatenate([[0], np.cumsum(plens)]).astype(np.int64)
+        self.cams = np.ascontiguousarray(np.concatenate(
+            [np.zeros(0)] + [np.asarray(c, np.float64).reshape(-1) for p in problems for c in p.camera_params]))
+        self.rq, self.rt = cat([p.rig_qvecs for p in problems], 4), cat([p.rig_tvecs for p in problems], 3)
+        self.q = np.ascontiguousarray(np.array([p.qvec for p in problems], np.float64).reshape(n, 4))
+        self.t = np.ascontiguousarray(np.array([p.tvec for p in problems], np.float64).reshape(n, 3))
+        self.cov = None
+        if covariance is True:
+            self.cov = np.zeros((n, 6, 6))
+        elif covariance is not False and covariance is not None:
+            self.cov = np.ascontiguousarray(covariance, dtype=np.float64).reshape(n, 6, 6).copy()
+        b = self.batch = GeneralizedPoseBatch()
+        b.num_problems = n
+        b.obs_offsets = _ptr(self.obs_off, _i64p)
+        b.points2D = _ptr(self.p2, _dp)
+        b.points3D = _ptr(self.p3, _dp)
+        b.inlier_mask = _ptr(self.mask, _u8p)
+        b.camera_idxs = _ptr(self.cidx, _i32p)
+        b.camera_offsets = _ptr(self.cam_off, _i64p)
+        b.camera_model_ids = _ptr(self.models, _i32p)
+        b.camera_param_offsets = _ptr(self.prm_off, _i64p)
+        b.camera_params = _ptr(self.cams, _dp)
+        b.rig_qvecs = _ptr(self.rq, _dp)
+        b.rig_tvecs = _ptr(self.rt, _dp)
+        b.qvec = _ptr(self.q, _dp)
+        b.tvec = _ptr(self.t, _dp)
+        b.rot_tvec_covariance = _ptr(self.cov, _dp)
+
+
+def generalized_pose_limits():
+    """(most cameras of a rig, largest tangent, most inlier correspondences
+    resident in LDS) of the generalized pose kernel."""
+    cams, tangent, cap = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    load().mi_ba_generalized_pose_limits(C.byref(cams), C.byref(tangent), C.byref(cap))
+    return cams.value, tangent.value, cap.value
+
+
+def generalized_pose_plan(options: PoseRefineOptions, problems):
+    """mi_ba_generalized_pose_plan: (statuses, tangent sizes, inlier counts)
+    per problem as the solve will see them.  Needs no device."""
+    a = _GeneralizedPoseArrays(problems)
+    st = np.zeros(a.n, np.int32)
+    tan = np.zeros(a.n, np.int32)
+    cnt = np.zeros(a.n, np.int64)
+    check(load().mi_ba_generalized_pose_plan(C.byref(options), C.byref(a.batch), _ptr(st, _i32p), _ptr(tan, _i32p),
+                                             _ptr(cnt, _i64p)), "mi_ba_generalized_pose_plan")
+    return st, tan, cnt
+
+
+def refine_generalized_absolute_pose_batch(options: PoseRefineOptions, problems, covariance=False,
+                                           trace: Optional[np.ndarray] = None) -> PoseBatchResult:
+    """mi_ba_refine_generalized_absolute_pose_batch: every rig problem of the
+    list in one launch.  As refine_absolute_pose_batch; camera_params of the
+    result is, per problem, the list of its cameras' parameter arrays."""
+    a = _GeneralizedPoseArrays(problems, covariance)
+    n = a.n
+    if trace is not None:
+        assert trace.dtype == np.uint8 and trace.flags.c_contiguous and trace.shape[0] == n
+    st = np.zeros(n, np.int32)
+    us = np.zeros(n, np.int32)
+    sums = (Summary * max(n, 1))()
+    if trace is not None:
+        load().mi_ba_pose_refine_set_trace(_ptr(trace, _u8p), int(trace.shape[1]))
+    try:
+        rc = load().mi_ba_refine_generalized_absolute_pose_batch(C.byref(options), C.byref(a.batch), _ptr(st, _i32p),
+                                                                 C.cast(sums, C.c_void_p), _ptr(us, _i32p))
+    finally:
+        if trace is not None:
+            load().mi_ba_pose_refine_set_trace(None, 0)
+    check(rc, "mi_ba_refine_generalized_absolute_pose_batch")
+    cams = [[a.cams[a.prm_off[c]:a.prm_off[c + 1]].copy() for c in range(a.cam_off[k], a.cam_off[k + 1])]
+            for k in range(n)]
+    return PoseBatchResult(st, list(sums)[:n], us, a.q, a.t, cams, a.cov)
 
 
 def pose_problem_scene(problem: PoseProblem) -> Scene:
