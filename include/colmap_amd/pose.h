@@ -11,7 +11,10 @@
 //
 // RefineGeneralizedAbsolutePose (estimators/pose.h:221-233; pose.cc:354-520),
 // the pose of a camera rig from the correspondences of several of its cameras,
-// follows below on mi_ba_refine_generalized_absolute_pose_batch.
+// follows below on mi_ba_refine_generalized_absolute_pose_batch, and
+// RefineRelativePose (estimators/pose.h:195; pose.cc:324-352), the two-view
+// refinement on the squared Sampson error, on mi_ba_refine_relative_pose_batch
+// with EssentialMatrixFromPose beside it.
 //
 // Differences to the reference: a qvec that is not of unit length is
 // normalised first; the linear solve is a Cholesky of the normal equations,
@@ -19,6 +22,7 @@
 #pragma once
 
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -351,6 +355,160 @@ inline bool RefineGeneralizedAbsolutePose(const AbsolutePoseRefinementOptions& o
   p.cameras = cameras;
   p.rot_tvec_covariance = rot_tvec_covariance;
   return RefineGeneralizedAbsolutePoses(options, {p})[0];
+}
+
+// RefineRelativePose (estimators/pose.h:195; pose.cc:324-352) on
+// mi_ba_refine_relative_pose_batch: the pose (qvec, tvec) of a second camera
+// against a first one at the origin, from correspondences in normalised image
+// coordinates.  Restated quirks of the reference, kept on purpose:
+//   * the residual is already the *squared* Sampson error and Ceres squares
+//     it once more (cost = 0.5 sum rho(r^2), rho = CauchyLoss(1.0));
+//   * qvec is normalised first, tvec is not; tvec moves on Ceres 2.1's
+//     SphereManifold<3> (a Householder chart), which keeps its length.
+// The reference takes a whole ceres::Solver::Options; the four fields that
+// matter to this solver are the options below, with Ceres' defaults.
+// Out of scope: RefineEssentialMatrix (its PoseFromEssentialMatrix needs an
+// SVD and a DLT triangulation this project does not have; inlier masks are
+// served by mi_ba_relative_pose_batch::inlier_mask), a covariance, and
+// EstimateRelativePose's RANSAC.
+struct RelativePoseRefinementOptions {
+  // ceres::Solver::Options' defaults.
+  int max_num_iterations = 50;
+  double function_tolerance = 1e-6;
+  double gradient_tolerance = 1e-10;
+  double parameter_tolerance = 1e-8;
+  // Scale of the Cauchy loss; 1.0 is the reference's kMaxL2Error (build addition).
+  double loss_function_scale = 1.0;
+  // HIP device ordinal (build addition).
+  int device = 0;
+
+  void Check() const {
+    if (max_num_iterations < 0) throw std::invalid_argument("max_num_iterations must be >= 0");
+    if (!(function_tolerance >= 0.0)) throw std::invalid_argument("function_tolerance must be >= 0");
+    if (!(gradient_tolerance >= 0.0)) throw std::invalid_argument("gradient_tolerance must be >= 0");
+    if (!(parameter_tolerance >= 0.0)) throw std::invalid_argument("parameter_tolerance must be >= 0");
+    if (!(loss_function_scale >= 0.0)) throw std::invalid_argument("loss_function_scale must be >= 0");
+  }
+};
+
+// One problem of RefineRelativePoses: the arguments of RefineRelativePose.
+struct RelativePoseProblem {
+  const std::vector<std::array<double, 2>>* points1 = nullptr;
+  const std::vector<std::array<double, 2>>* points2 = nullptr;
+  std::array<double, 4>* qvec = nullptr;
+  std::array<double, 3>* tvec = nullptr;
+};
+
+// Refines every image pair in one call; returns per problem Ceres'
+// IsSolutionUsable.  summaries (nullable) receives the solver summaries.
+inline std::vector<bool> RefineRelativePoses(const RelativePoseRefinementOptions& options,
+                                             const std::vector<RelativePoseProblem>& problems,
+                                             std::vector<SolverSummary>* summaries = nullptr) {
+  const int n = (int)problems.size();
+  std::vector<int64_t> obs_off(n + 1, 0);
+  for (int k = 0; k < n; ++k) {
+    const RelativePoseProblem& p = problems[k];
+    if (!p.points1 || !p.points2 || !p.qvec || !p.tvec) throw std::invalid_argument("RefineRelativePose: null argument");
+    // CHECK_EQ(points1.size(), points2.size())
+    if (p.points1->size() != p.points2->size()) throw std::invalid_argument("points1.size() != points2.size()");
+    obs_off[k + 1] = obs_off[k] + (int64_t)p.points1->size();
+  }
+  options.Check();
+  if (summaries) summaries->assign(n, SolverSummary());
+  std::vector<bool> usable(n, false);
+  if (n == 0) return usable;
+  const size_t N = (size_t)obs_off[n];
+  std::vector<double> p1(2 * N), p2(2 * N), q(4 * (size_t)n), t(3 * (size_t)n);
+  for (int k = 0; k < n; ++k) {
+    const RelativePoseProblem& p = problems[k];
+    for (size_t i = 0; i < p.points1->size(); ++i) {
+      const size_t o = (size_t)obs_off[k] + i;
+      p1[2 * o] = (*p.points1)[i][0];
+      p1[2 * o + 1] = (*p.points1)[i][1];
+      p2[2 * o] = (*p.points2)[i][0];
+      p2[2 * o + 1] = (*p.points2)[i][1];
+    }
+    for (int m = 0; m < 4; ++m) q[4 * (size_t)k + m] = (*p.qvec)[m];
+    for (int m = 0; m < 3; ++m) t[3 * (size_t)k + m] = (*p.tvec)[m];
+  }
+  mi_ba_relative_pose_options o;
+  mi_ba_default_relative_pose_options(&o);
+  o.max_num_iterations = options.max_num_iterations;
+  o.function_tolerance = options.function_tolerance;
+  o.gradient_tolerance = options.gradient_tolerance;
+  o.parameter_tolerance = options.parameter_tolerance;
+  o.loss_function_scale = options.loss_function_scale;
+  o.device = options.device;
+  mi_ba_relative_pose_batch b{};
+  b.num_problems = n;
+  b.obs_offsets = obs_off.data();
+  b.points1 = p1.data();
+  b.points2 = p2.data();
+  b.qvec = q.data();
+  b.tvec = t.data();
+  std::vector<int32_t> statuses(n), ok(n);
+  std::vector<mi_ba_summary> sums(n);
+  const mi_ba_status st = mi_ba_refine_relative_pose_batch(&o, &b, statuses.data(), sums.data(), ok.data());
+  if (st == MI_BA_ERR_INVALID_ARGUMENT) throw std::invalid_argument("RefineRelativePose: invalid argument");
+  if (st != MI_BA_OK) throw std::runtime_error(std::string("RefineRelativePose: ") + mi_ba_status_string(st));
+  for (int k = 0; k < n; ++k) {
+    const RelativePoseProblem& p = problems[k];
+    if (statuses[k] != MI_BA_OK) throw std::runtime_error(std::string("RefineRelativePose: ") + mi_ba_status_string(statuses[k]));
+    SolverSummary s;
+    s.num_residuals_reduced = sums[k].num_residuals_reduced;
+    s.num_effective_parameters_reduced = sums[k].num_effective_parameters_reduced;
+    s.num_successful_steps = sums[k].num_successful_steps;
+    s.num_unsuccessful_steps = sums[k].num_unsuccessful_steps;
+    s.termination_type = (SolverSummary::TerminationType)sums[k].termination_type;
+    s.initial_cost = sums[k].initial_cost;
+    s.final_cost = sums[k].final_cost;
+    s.num_jacobian_evaluations = sums[k].num_jacobian_evaluations;
+    s.num_linear_solver_iterations = sums[k].num_linear_solver_iterations;
+    if (summaries) (*summaries)[k] = s;
+    // the library writes parameters back only where Ceres would
+    for (int m = 0; m < 4; ++m) (*p.qvec)[m] = q[4 * (size_t)k + m];
+    for (int m = 0; m < 3; ++m) (*p.tvec)[m] = t[3 * (size_t)k + m];
+    usable[k] = ok[k] != 0;
+  }
+  return usable;
+}
+
+// RefineRelativePose (pose.cc:324-352), the reference's argument order.
+inline bool RefineRelativePose(const RelativePoseRefinementOptions& options,
+                               const std::vector<std::array<double, 2>>& points1,
+                               const std::vector<std::array<double, 2>>& points2, std::array<double, 4>* qvec,
+                               std::array<double, 3>* tvec) {
+  RelativePoseProblem p;
+  p.points1 = &points1;
+  p.points2 = &points2;
+  p.qvec = qvec;
+  p.tvec = tvec;
+  return RefineRelativePoses(options, {p})[0];
+}
+
+// EssentialMatrixFromPose (src/base/essential_matrix.cc:90-93):
+// [t / |t|]x R, row-major.
+inline std::array<double, 9> EssentialMatrixFromPose(const std::array<double, 9>& R, const std::array<double, 3>& tvec) {
+  const double nt = std::sqrt(tvec[0] * tvec[0] + tvec[1] * tvec[1] + tvec[2] * tvec[2]);
+  const double t[3] = {nt > 0 ? tvec[0] / nt : tvec[0], nt > 0 ? tvec[1] / nt : tvec[1], nt > 0 ? tvec[2] / nt : tvec[2]};
+  std::array<double, 9> E;
+  for (int c = 0; c < 3; ++c) {
+    E[c] = t[1] * R[6 + c] - t[2] * R[3 + c];
+    E[3 + c] = t[2] * R[c] - t[0] * R[6 + c];
+    E[6 + c] = t[0] * R[3 + c] - t[1] * R[c];
+  }
+  return E;
+}
+
+// The same from a quaternion (w, x, y, z), normalised first (QuaternionToRotationMatrix).
+inline std::array<double, 9> EssentialMatrixFromPose(const std::array<double, 4>& qvec, const std::array<double, 3>& tvec) {
+  const double nq = std::sqrt(qvec[0] * qvec[0] + qvec[1] * qvec[1] + qvec[2] * qvec[2] + qvec[3] * qvec[3]);
+  const double w = nq > 0 ? qvec[0] / nq : 1.0, x = nq > 0 ? qvec[1] / nq : 0.0, y = nq > 0 ? qvec[2] / nq : 0.0,
+               z = nq > 0 ? qvec[3] / nq : 0.0;
+  const std::array<double, 9> R{{1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                                 2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                                 2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)}};
+  return EssentialMatrixFromPose(R, tvec);
 }
 
 }  // namespace colmap_amd

@@ -32,6 +32,9 @@
  *   mi_ba_refine_absolute_pose_batch
  *                              <- RefineAbsolutePose (src/estimators/pose.cc:198-322), many
  *                                 problems per call
+ *   mi_ba_refine_relative_pose_batch
+ *                              <- RefineRelativePose (src/estimators/pose.cc:324-352), many
+ *                                 image pairs per call
  *   mi_ba_semantic (struct)    <- SemanticBundleAdjustmentOptions depth/semantic maps
  *                                 (src/optim/semantic_bundle_adjustment.h:53-140,
  *                                 semantic_bundle_adjustment.cc:699-906,1021-1068)
@@ -932,6 +935,84 @@ void mi_ba_generalized_pose_limits(int32_t* max_cameras, int32_t* max_tangent, i
 mi_ba_status mi_ba_generalized_pose_plan(const mi_ba_pose_refine_options* options,
                                          const mi_ba_generalized_pose_batch* batch, int32_t* statuses,
                                          int32_t* tangent_sizes, int64_t* inlier_counts);
+
+/* --- batched relative-pose (two-view) refinement ----------------------------
+ * Additive entry points (MI_BA_ABI_VERSION stays 4).
+ * RefineRelativePose (src/estimators/pose.cc:324-352): the pose (q, t) of a
+ * second camera against a first one at the origin, from correspondences in
+ * normalised image coordinates; no camera model is involved.  Per
+ * correspondence (x1, y1) <-> (x2, y2), with R = ceres::QuaternionToRotation(q)
+ * and E = [t]x R:
+ *     a = E (x1, y1, 1)',  b = E' (x2, y2, 1)',  s = (x2, y2, 1) . a,
+ *     r = s^2 / (a0^2 + a1^2 + b0^2 + b1^2).
+ * The residual r is already the *squared* Sampson error
+ * (RelativePoseCostFunction, cost_functions.h:256-258) and Ceres squares it
+ * once more: the cost is 0.5 sum rho(r^2), rho = CauchyLoss(loss_function_scale).
+ * That is the reference's behaviour and is kept.  q is normalised first
+ * (pose.cc:331) and lives on QuaternionManifold; t is not normalised and lives
+ * on Ceres 2.1's SphereManifold<3> (a Householder chart; Plus keeps |t|): the
+ * tangent is 3 + 2.  The caller's ceres::Solver::Options are the four fields
+ * below; the rest is Ceres' default as in mi_ba_refine_absolute_pose_batch
+ * (radius 1e4, min relative decrease 1e-3, 5 consecutive invalid steps, Jacobi
+ * scaling, a Cholesky of the normal equations).
+ *
+ * Out of scope: RefineEssentialMatrix and its PoseFromEssentialMatrix
+ * decomposition, a covariance, and EstimateRelativePose's RANSAC. */
+typedef struct mi_ba_relative_pose_options {
+  int32_t max_num_iterations;   /* default 50 */
+  double function_tolerance;    /* default 1e-6 */
+  double gradient_tolerance;    /* default 1e-10 */
+  double parameter_tolerance;   /* default 1e-8 */
+  double loss_function_scale;   /* default 1.0 = the reference's kMaxL2Error; build addition */
+  int32_t device;               /* HIP device ordinal, default 0 */
+} mi_ba_relative_pose_options;
+
+/* Zeroes the struct (padding included), then sets the defaults above. */
+void mi_ba_default_relative_pose_options(mi_ba_relative_pose_options* options);
+
+/* A batch of problems as a struct of arrays.  Problem k owns the
+ * correspondences obs_offsets[k] .. obs_offsets[k + 1).  inlier_mask is a
+ * build addition (RefineEssentialMatrix-style callers skip their compaction
+ * copy, essential_matrix.cc:177-186): a masked call gives the bits of the
+ * call on the compacted arrays. */
+typedef struct mi_ba_relative_pose_batch {
+  int32_t num_problems;
+  const int64_t* obs_offsets;   /* [num_problems + 1] */
+  const double* points1;        /* [obs_offsets[n]][2] normalised image coordinates */
+  const double* points2;        /* [obs_offsets[n]][2] */
+  const uint8_t* inlier_mask;   /* nullable (= all inliers); nonzero = used */
+  double* qvec;                 /* (in/out) [num_problems][4] (w,x,y,z) */
+  double* tvec;                 /* (in/out) [num_problems][3] */
+} mi_ba_relative_pose_batch;
+
+/* Solves every problem of the batch in one launch (one wavefront per problem,
+ * the whole Levenberg-Marquardt loop on the device).  statuses, summaries and
+ * usable as in mi_ba_refine_absolute_pose_batch: num_residuals_reduced is the
+ * inlier count (one residual per correspondence),
+ * num_effective_parameters_reduced 5; a problem without inliers does nothing
+ * (CONVERGENCE, usable 1); with max_num_iterations 0 only the initial cost is
+ * evaluated (NO_CONVERGENCE, usable 1, q normalised).  A non-finite initial
+ * cost (t = 0, a correspondence whose denominator vanishes) ends in
+ * MI_BA_FAILURE: usable 0, parameters untouched; a non-finite candidate cost
+ * is an unsuccessful step.  MI_BA_ERR_INVALID_ARGUMENT, before any device is
+ * touched, for a negative tolerance, iteration limit, scale or problem count
+ * and for offsets that decrease.  Honours mi_ba_pose_refine_set_trace.  Every
+ * sum runs in a fixed order without atomics: a problem gives the same bits on
+ * every run, at every position of a batch and alone. */
+mi_ba_status mi_ba_refine_relative_pose_batch(const mi_ba_relative_pose_options* options,
+                                              const mi_ba_relative_pose_batch* batch, int32_t* statuses,
+                                              mi_ba_summary* summaries, int32_t* usable);
+
+/* Most inlier correspondences of one problem that the kernel keeps resident
+ * in LDS; a problem with more streams them from device memory. */
+int32_t mi_ba_relative_pose_lds_capacity(void);
+
+/* residuals [obs_offsets[n]] and jacobians [obs_offsets[n]][5] (rotation
+ * tangent 3, sphere tangent 2) of every correspondence, not loss-corrected, at
+ * the given q, t (q is not normalised here; the mask is ignored). */
+mi_ba_status mi_ba_relative_pose_evaluate(const mi_ba_relative_pose_options* options,
+                                          const mi_ba_relative_pose_batch* batch, double* residuals,
+                                          double* jacobians);
 
 /* Per-kernel HIP-event timing on the context's stream (enabled with
  * mi_ba_set_timing).  name: "reproj_jacobian", "semantic_jacobian", ... */

@@ -306,6 +306,30 @@ class GeneralizedPoseBatch(C.Structure):
     ]
 
 
+class RelativePoseOptions(C.Structure):
+    """mi_ba_relative_pose_options (the ceres::Solver::Options fields RefineRelativePose's caller sets)."""
+    _fields_ = [
+        ("max_num_iterations", C.c_int32),
+        ("function_tolerance", C.c_double),
+        ("gradient_tolerance", C.c_double),
+        ("parameter_tolerance", C.c_double),
+        ("loss_function_scale", C.c_double),
+        ("device", C.c_int32),
+    ]
+
+
+class RelativePoseBatch(C.Structure):
+    _fields_ = [
+        ("num_problems", C.c_int32),
+        ("obs_offsets", _i64p),
+        ("points1", _dp),
+        ("points2", _dp),
+        ("inlier_mask", _u8p),
+        ("qvec", _dp),
+        ("tvec", _dp),
+    ]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [
         ("camera_model", C.c_int32),
@@ -417,6 +441,13 @@ def load(path: str = LIB_PATH):
                                                 _i32p, _i64p]
     lib.mi_ba_pose_refine_lds_capacity.argtypes = []
     lib.mi_ba_pose_refine_lds_capacity.restype = C.c_int32
+    lib.mi_ba_default_relative_pose_options.argtypes = [C.POINTER(RelativePoseOptions)]
+    lib.mi_ba_default_relative_pose_options.restype = None
+    lib.mi_ba_refine_relative_pose_batch.argtypes = [C.POINTER(RelativePoseOptions), C.POINTER(RelativePoseBatch),
+                                                     _i32p, C.c_void_p, _i32p]
+    lib.mi_ba_relative_pose_evaluate.argtypes = [C.POINTER(RelativePoseOptions), C.POINTER(RelativePoseBatch), _dp, _dp]
+    lib.mi_ba_relative_pose_lds_capacity.argtypes = []
+    lib.mi_ba_relative_pose_lds_capacity.restype = C.c_int32
     _lib = lib
     return lib
 
@@ -1214,6 +1245,115 @@ def refine_generalized_absolute_pose_batch(options: PoseRefineOptions, problems,
     cams = [[a.cams[a.prm_off[c]:a.prm_off[c + 1]].copy() for c in range(a.cam_off[k], a.cam_off[k + 1])]
             for k in range(n)]
     return PoseBatchResult(st, list(sums)[:n], us, a.q, a.t, cams, a.cov)
+
+
+def default_relative_pose_options(**kw) -> RelativePoseOptions:
+    o = RelativePoseOptions()
+    load().mi_ba_default_relative_pose_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def relative_pose_lds_capacity() -> int:
+    return int(load().mi_ba_relative_pose_lds_capacity())
+
+
+@dataclass
+class RelativePoseProblem:
+    """One RefineRelativePose problem (estimators/pose.h:195): correspondences
+    in normalised image coordinates and the pose of the second camera."""
+    qvec: np.ndarray                     # [4]
+    tvec: np.ndarray                     # [3]
+    points1: np.ndarray                  # [N][2]
+    points2: np.ndarray                  # [N][2]
+    inlier_mask: Optional[np.ndarray] = None  # [N], nonzero = inlier (None: all)
+
+    def copy(self) -> "RelativePoseProblem":
+        return RelativePoseProblem(np.array(self.qvec, np.float64), np.array(self.tvec, np.float64),
+                                   np.array(self.points1, np.float64), np.array(self.points2, np.float64),
+                                   None if self.inlier_mask is None else np.array(self.inlier_mask))
+
+
+@dataclass
+class RelativePoseBatchResult:
+    statuses: np.ndarray                 # [n] mi_ba_status per problem
+    summaries: list                      # [n] Summary
+    usable: np.ndarray                   # [n] 0 / 1
+    qvec: np.ndarray                     # [n][4]
+    tvec: np.ndarray                     # [n][3]
+
+
+class _RelativePoseArrays:
+    """The struct of arrays of a list of RelativePoseProblem (kept alive
+    beside the ctypes struct that points into it)."""
+
+    def __init__(self, problems):
+        n = self.n = len(problems)
+        counts = [int(np.asarray(p.points1).reshape(-1, 2).shape[0]) for p in problems]
+        for p, c in zip(problems, counts):
+            if np.asarray(p.points2).reshape(-1, 2).shape[0] != c:
+                raise ValueError("points1 and points2 differ in length")
+            if p.inlier_mask is not None and len(p.inlier_mask) != c:
+                raise ValueError("inlier_mask and points1 differ in length")
+        cat = lambda xs: (np.ascontiguousarray(np.concatenate([np.asarray(x, np.float64).reshape(-1, 2) for x in xs]))
+                          if n else np.zeros((0, 2)))
+        self.obs_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        self.p1, self.p2 = cat([p.points1 for p in problems]), cat([p.points2 for p in problems])
+        self.mask = None
+        if any(p.inlier_mask is not None for p in problems):
+            self.mask = np.ascontiguousarray(np.concatenate(
+                [np.ones(c, np.uint8) if p.inlier_mask is None else (np.asarray(p.inlier_mask) != 0).astype(np.uint8)
+                 for p, c in zip(problems, counts)]))
+        self.q = np.ascontiguousarray(np.array([p.qvec for p in problems], np.float64).reshape(n, 4))
+        self.t = np.ascontiguousarray(np.array([p.tvec for p in problems], np.float64).reshape(n, 3))
+        b = self.batch = RelativePoseBatch()
+        b.num_problems = n
+        b.obs_offsets = _ptr(self.obs_off, _i64p)
+        b.points1 = _ptr(self.p1, _dp)
+        b.points2 = _ptr(self.p2, _dp)
+        b.inlier_mask = _ptr(self.mask, _u8p)
+        b.qvec = _ptr(self.q, _dp)
+        b.tvec = _ptr(self.t, _dp)
+
+
+def refine_relative_pose_batch(options: RelativePoseOptions, problems,
+                               trace: Optional[np.ndarray] = None) -> RelativePoseBatchResult:
+    """mi_ba_refine_relative_pose_batch: every two-view problem of the list in
+    one launch.  The problems are not modified; the refined poses come back
+    in the result.  trace: a uint8 array [n][cap] that receives the LM trace
+    (mi_ba_pose_refine_set_trace)."""
+    a = _RelativePoseArrays(problems)
+    n = a.n
+    if trace is not None:
+        assert trace.dtype == np.uint8 and trace.flags.c_contiguous and trace.shape[0] == n
+    st = np.zeros(n, np.int32)
+    us = np.zeros(n, np.int32)
+    sums = (Summary * max(n, 1))()
+    if trace is not None:
+        load().mi_ba_pose_refine_set_trace(_ptr(trace, _u8p), int(trace.shape[1]))
+    try:
+        rc = load().mi_ba_refine_relative_pose_batch(C.byref(options), C.byref(a.batch), _ptr(st, _i32p),
+                                                     C.cast(sums, C.c_void_p), _ptr(us, _i32p))
+    finally:
+        if trace is not None:
+            load().mi_ba_pose_refine_set_trace(None, 0)
+    check(rc, "mi_ba_refine_relative_pose_batch")
+    return RelativePoseBatchResult(st, list(sums)[:n], us, a.q, a.t)
+
+
+def relative_pose_evaluate(options: RelativePoseOptions, problems):
+    """mi_ba_relative_pose_evaluate: per problem (residuals [N], jacobians
+    [N][5]: rotation tangent 3, sphere tangent 2), not loss-corrected, at the
+    given q, t."""
+    a = _RelativePoseArrays(problems)
+    total = int(a.obs_off[-1])
+    r, J = np.zeros(total), np.zeros((total, 5))
+    check(load().mi_ba_relative_pose_evaluate(C.byref(options), C.byref(a.batch), _ptr(r, _dp), _ptr(J, _dp)),
+          "mi_ba_relative_pose_evaluate")
+    return [(r[a.obs_off[k]:a.obs_off[k + 1]].copy(), J[a.obs_off[k]:a.obs_off[k + 1]].copy()) for k in range(a.n)]
 
 
 def pose_problem_scene(problem: PoseProblem) -> Scene:
