@@ -87,37 +87,6 @@ struct GPoseArgs {
   int32_t trace_cap;
 };
 
-__device__ __forceinline__ void gpose_trace(const GPoseArgs& a, int index, int it, int valid, int successful, int end) {
-  if (a.trace && it >= 1 && it <= a.trace_cap)
-    a.trace[(size_t)index * a.trace_cap + it - 1] = (uint8_t)(valid | successful << 1 | end << 2);
-}
-
-struct GObsSource {
-  const double* sx;      // LDS, SoA in grouped order (resident) ...
-  const int32_t* order;  // ... or device memory through the grouped list
-  const double2* p2;
-  const double* p3;
-  bool resident;
-  int lds_obs;
-  __device__ __forceinline__ void load(int i, double* ox, double* oy, double X[3]) const {
-    if (resident) {
-      *ox = sx[i];
-      *oy = sx[lds_obs + i];
-      X[0] = sx[2 * lds_obs + i];
-      X[1] = sx[3 * lds_obs + i];
-      X[2] = sx[4 * lds_obs + i];
-    } else {
-      const size_t j = (size_t)order[i];
-      const double2 o = p2[j];
-      *ox = o.x;
-      *oy = o.y;
-      X[0] = p3[3 * j];
-      X[1] = p3[3 * j + 1];
-      X[2] = p3[3 * j + 2];
-    }
-  }
-};
-
 // Camera-frame point of the rig camera: P = R_rel (R(q) X + t) + t_rel; a = R(q) X.
 __device__ __forceinline__ void gpose_point(const double* rig, const double* rel, const double X[3], double a[3],
                                             double P[3]) {
@@ -180,6 +149,10 @@ __device__ inline void gpose_obs_rows(int model, const double* rig, const double
   rotation_tangent_jacobian(q, X, a[0], a[1], a[2], true, quat_is_unit(q), Mq);
   emit_row_pose(0, J0, BR, Mq, true, 0u);
   emit_row_pose(1, J1, BR, Mq, true, 0u);
+  // The refined-intrinsics columns and the residual column.  Kept in this
+  // function, not in a helper shared with pose_obs_rows: moved into one, the
+  // compiler pairs the products of the camera model's Jacobian differently and
+  // a last bit of [J r]'[J r] changes.
   if constexpr (LT > 6) {
 #pragma unroll
     for (int m = 0; m < LT - 6; ++m) {
@@ -196,52 +169,6 @@ __device__ inline void gpose_obs_rows(int model, const double* rig, const double
   }
   J0[LT] = r0 * sc;
   J1[LT] = r1 * sc;
-}
-
-// Dense Cholesky by one wave, in LDS: lane i < n owns row i of the lower
-// triangle in sA (row stride S); on return sA holds L.  A pivot k with
-// !(pivot > tol * d0[k]) makes the result false.
-__device__ inline bool gwave_cholesky(double* sA, int S, int n, int lane, double tol, const double* d0) {
-  bool ok = true;
-#pragma unroll 1
-  for (int k = 0; k < n; ++k) {
-    wave_sync();
-    const double akk = sA[k * S + k];
-    if (!(akk > tol * d0[k])) ok = false;
-    const double lkk = sqrt(akk);
-    const bool mine = lane < n && lane >= k;
-    double lik = 0.0;
-    if (mine) lik = lane == k ? lkk : sA[lane * S + k] / lkk;
-    wave_sync();
-    if (mine) sA[lane * S + k] = lik;
-    wave_sync();
-    if (mine)
-      for (int j = k + 1; j <= lane; ++j) sA[lane * S + j] -= lik * sA[j * S + k];
-  }
-  wave_sync();
-  return ok;
-}
-
-// Solves L L' x = b with L in sA: lane i < n passes b_i and receives x_i.
-__device__ inline double gwave_chol_solve(const double* sA, int S, int n, double b, int lane, double* sx) {
-#pragma unroll 1
-  for (int k = 0; k < n; ++k) {
-    if (lane == k) sx[k] = b / sA[k * S + k];
-    wave_sync();
-    const double yk = sx[k];
-    if (lane == k) b = yk;
-    else if (lane > k && lane < n) b -= sA[lane * S + k] * yk;
-  }
-#pragma unroll 1
-  for (int k = n - 1; k >= 0; --k) {
-    if (lane == k) sx[k] = b / sA[k * S + k];
-    wave_sync();
-    const double xk = sx[k];
-    if (lane == k) b = xk;
-    else if (lane < k) b -= sA[k * S + lane] * xk;
-  }
-  wave_sync();
-  return b;
 }
 
 // LT: width of one camera's local tangent (6: no intrinsics refined anywhere
@@ -285,31 +212,22 @@ __global__ __launch_bounds__(kPoseTB) void generalized_pose_kernel(GPoseArgs a) 
   int* sTan = sCam + kGMaxCams * kGCamInts;  // tangent column -> index into sState
   int* sSegCam = sTan + 64;
   double* sObs = lds + L::kFixed;
+  const PoseLmLds<NCG, S, 64, true> solve{sM, sA, sScale, sStep, sD0, lm, sTan};
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const GProblemDev* pb = a.prob + blockIdx.x;
   const int count = pb->count, ncam = pb->ncam, n = pb->n, index = pb->index, nseg = pb->nseg, ntiles = pb->ntiles;
   const int nstate = 8 + 8 * ncam;
-  double* out = a.out + (size_t)index * kOutStride;
+  const PoseLmOptions opt{a.gradient_tolerance, a.max_num_iterations, a.trace, a.trace_cap, index};
   const GTile* tiles = a.tiles + pb->tile_begin;
-  GObsSource src;
+  PoseObsSource<true> src;
   src.lds_obs = a.lds_obs;
   src.resident = count <= a.lds_obs;
   src.sx = sObs;
   src.order = a.order + pb->obs_begin;
   src.p2 = a.p2 + pb->raw_begin;
   src.p3 = a.p3 + 3 * pb->raw_begin;
-  if (src.resident) {
-    for (int i = tid; i < count; i += kPoseTB) {
-      const size_t j = (size_t)src.order[i];
-      const double2 o = src.p2[j];
-      sObs[i] = o.x;
-      sObs[a.lds_obs + i] = o.y;
-      sObs[2 * a.lds_obs + i] = src.p3[3 * j];
-      sObs[3 * a.lds_obs + i] = src.p3[3 * j + 1];
-      sObs[4 * a.lds_obs + i] = src.p3[3 * j + 2];
-    }
-  }
+  src.stage(tid, count);
   if (tid < 8) sState[tid] = a.rig[(size_t)index * 8 + tid];
   for (int i = tid; i < 8 * ncam; i += kPoseTB) sState[8 + i] = a.cprm[8 * (size_t)pb->cam_begin + i];
   for (int i = tid; i < ncam * 12; i += kPoseTB) sRel[i] = a.cams[pb->cam_begin + i / 12].rel[i % 12];
@@ -321,28 +239,12 @@ __global__ __launch_bounds__(kPoseTB) void generalized_pose_kernel(GPoseArgs a) 
     for (int k = 0; k < c->ct; ++k) sTan[c->off + k] = 8 + 8 * tid + c->idx[k];
   }
   if (tid < nseg) sSegCam[tid] = pb->seg_cam[tid];
-  if (tid == 0) {
-    lm->radius = kInitialRadius;
-    lm->decrease_factor = 2.0;
-    lm->iteration = 0;
-    lm->consecutive_invalid = 0;
-    lm->n_successful = 0;
-    lm->n_unsuccessful = 0;
-    lm->termination = MI_BA_NO_CONVERGENCE;
-    lm->last_successful = 1;  // iteration 0 counts as successful (IterationZero)
-  }
+  solve.init(tid);
   __syncthreads();
 
-  // the lane's entries (i, j), i <= j < LC, of a camera's upper triangle
+  // the lane's entries of a camera's upper triangle
   int ei[EPL], ej[EPL];
-#pragma unroll
-  for (int s = 0; s < EPL; ++s) {
-    int e = lane + 64 * s, i = 0, w = LC;
-    if (e >= NE) e = 0;  // idle slot: sums entry 0, never stored
-    while (e >= w) { e -= w; --w; ++i; }
-    ei[s] = i;
-    ej[s] = i + e;
-  }
+  pose_triangle_entries<LC>(lane, ei, ej);
   const int tile0 = pb->wave_tile[wave], tile1 = pb->wave_tile[wave + 1];
 
   bool first = true;
@@ -372,34 +274,17 @@ __global__ __launch_bounds__(kPoseTB) void generalized_pose_kernel(GPoseArgs a) 
 #pragma unroll
           for (int s = 0; s < EPL; ++s) acc[s] = 0.0;
         }
-        {
-          double J0[LC], J1[LC];
+        double J0[LC], J1[LC];
 #pragma unroll
-          for (int c = 0; c < LC; ++c) { J0[c] = 0.0; J1[c] = 0.0; }
-          if (lane < tl.count) {
-            double ox, oy, X[3], cost;
-            src.load(tl.start + lane, &ox, &oy, X);
-            gpose_obs_rows<LT>(model, sState, sState + 8 + 8 * cam, sRel + 12 * cam, idx, ct, a.loss_scale, ox, oy, X,
-                               J0, J1, &cost);
-            cost_acc += cost;
-          }
-#pragma unroll
-          for (int c = 0; c < LC; ++c) {
-            slab[c * kColStride + lane] = J0[c];
-            slab[c * kColStride + 64 + lane] = J1[c];
-          }
+        for (int c = 0; c < LC; ++c) { J0[c] = 0.0; J1[c] = 0.0; }
+        if (lane < tl.count) {
+          double ox, oy, X[3], cost;
+          src.load(tl.start + lane, &ox, &oy, X);
+          gpose_obs_rows<LT>(model, sState, sState + 8 + 8 * cam, sRel + 12 * cam, idx, ct, a.loss_scale, ox, oy, X,
+                             J0, J1, &cost);
+          cost_acc += cost;
         }
-        wave_sync();
-#pragma unroll
-        for (int s = 0; s < EPL; ++s) {
-          const double* ci = slab + ei[s] * kColStride;
-          const double* cj = slab + ej[s] * kColStride;
-          double v = acc[s];
-#pragma unroll 4
-          for (int k = 0; k < 128; ++k) v += ci[k] * cj[k];
-          acc[s] = v;
-        }
-        wave_sync();
+        pose_tile_products<LC>(slab, lane, J0, J1, ei, ej, acc);
       }
       if (seg >= 0) {
 #pragma unroll
@@ -428,116 +313,15 @@ __global__ __launch_bounds__(kPoseTB) void generalized_pose_kernel(GPoseArgs a) 
         }
         const double total = pose_cost_total(sCost, lane);
         wave_sync();
-        if (first) {
-          sScale[lane] = lane < n ? 1.0 / (1.0 + sqrt(sM[lane * NCG + lane])) : 1.0;
-          if (lane == 0) {
-            lm->x_cost = total;
-            lm->initial_cost = total;
-          }
-          wave_sync();
-        }
+        if (first) solve.first(n, lane, total);
       }
       first = false;
     }
 
     if (wave == 0) {
       int act = kActStop;
-      // a non-finite initial cost: FAILURE, parameters untouched
-      bool go = isfinite(lm->x_cost);
-      if (!go && lane == 0) lm->termination = MI_BA_FAILURE;
-      while (go) {
-        // FinalizeIterationAndCheckIfMinimizerCanContinue
-        if (lm->iteration >= a.max_num_iterations) {
-          if (lane == 0) lm->termination = MI_BA_NO_CONVERGENCE;
-          break;
-        }
-        if (lm->last_successful) {
-          // GradientToleranceReached: |x - Plus(x, -g)|_inf, g = J'r
-          const double d[3] = {-sM[0 * NCG + NTG], -sM[1 * NCG + NTG], -sM[2 * NCG + NTG]};
-          const double q[4] = {sState[0], sState[1], sState[2], sState[3]};
-          double qn[4], gmax = 0.0;
-          quat_plus(q, d, qn);
-#pragma unroll
-          for (int m = 0; m < 4; ++m) gmax = fmax(gmax, fabs(q[m] - qn[m]));
-          for (int m = 0; m < 3; ++m)
-            gmax = fmax(gmax, fabs(sState[4 + m] - (sState[4 + m] + -sM[(3 + m) * NCG + NTG])));
-          for (int m = 6; m < n; ++m) {
-            const double xv = sState[sTan[m]];
-            gmax = fmax(gmax, fabs(xv - (xv + -sM[m * NCG + NTG])));
-          }
-          if (gmax <= a.gradient_tolerance) {
-            if (lane == 0) lm->termination = MI_BA_CONVERGENCE;
-            break;
-          }
-        }
-        const double radius = lm->radius;
-        if (radius <= kMinRadius) {
-          if (lane == 0) lm->termination = MI_BA_CONVERGENCE;
-          break;
-        }
-        wave_sync();
-        if (lane == 0) lm->iteration += 1;
-        // row `lane` of the scaled, damped system; LM diagonal: the clipped
-        // scaled column norm over the radius
-        const double scale = sScale[lane];
-        double gs = 0.0;
-        if (lane < n) {
-          for (int j = 0; j <= lane; ++j) {
-            double v = sM[lane * NCG + j] * scale * sScale[j];
-            if (j == lane) v = v + fmin(fmax(v, 1e-6), 1e32) / radius;
-            sA[lane * S + j] = v;
-          }
-          sD0[lane] = 1.0;
-          gs = sM[lane * NCG + NTG] * scale;
-        }
-        bool ok = gwave_cholesky(sA, S, n, lane, 0.0, sD0);
-        double step = 0.0, model = 0.0;
-        if (ok) {
-          // Ceres solves (J'J + D'D) x = J'r, step = -x
-          step = -gwave_chol_solve(sA, S, n, gs, lane, sStep);
-          sStep[lane] = lane < n ? step : 0.0;
-          wave_sync();
-          double term = 0.0;
-          if (lane < n) {
-            double hstep = 0.0;
-            for (int j = 0; j < n; ++j) hstep += sM[lane * NCG + j] * scale * sScale[j] * sStep[j];
-            term = step * (gs + 0.5 * hstep);
-          }
-          model = -wave_sum_fixed(term);
-          ok = isfinite(model) && model > 0.0;
-        }
-        if (!ok) {
-          const int inv = lm->consecutive_invalid + 1;
-          const double df = lm->decrease_factor;
-          wave_sync();
-          if (lane == 0) {
-            lm->last_successful = 0;
-            lm->consecutive_invalid = inv;
-            lm->n_unsuccessful += 1;
-            lm->radius = radius / df;
-            lm->decrease_factor = df * 2.0;
-            if (inv > kMaxConsecutiveInvalid) lm->termination = MI_BA_FAILURE;
-            gpose_trace(a, index, lm->iteration, 0, 0, inv > kMaxConsecutiveInvalid ? 1 : 0);
-          }
-          wave_sync();
-          if (inv > kMaxConsecutiveInvalid) break;
-          continue;
-        }
-        // candidate = Plus(x, step * scale)
-        const double delta = step * scale;
-        for (int m = lane; m < nstate; m += 64) sCand[m] = sState[m];
-        sStep[lane] = lane < n ? delta : 0.0;
-        wave_sync();
-        {
-          const double dq[3] = {sStep[0], sStep[1], sStep[2]};
-          const double q[4] = {sState[0], sState[1], sState[2], sState[3]};
-          double qn[4];
-          quat_plus(q, dq, qn);
-          if (lane < 4) sCand[lane] = lane == 0 ? qn[0] : lane == 1 ? qn[1] : lane == 2 ? qn[2] : qn[3];
-          if (lane >= 3 && lane < 6) sCand[1 + lane] = sState[1 + lane] + delta;
-          if (lane >= 6 && lane < n) sCand[sTan[lane]] = sState[sTan[lane]] + delta;
-        }
-        wave_sync();
+      double model_cost_change;
+      if (solve.propose(sState, sCand, nstate, n, lane, opt, &model_cost_change)) {
         // |x|^2, |x - candidate|^2 over the variable blocks in ambient
         // coordinates: qvec, tvec, and every parameter of a refined camera
         double xn2 = 0.0, sn2 = 0.0;
@@ -546,6 +330,7 @@ __global__ __launch_bounds__(kPoseTB) void generalized_pose_kernel(GPoseArgs a) 
           xn2 += xv * xv;
           sn2 += dv * dv;
         }
+#pragma unroll 1  // rolled, as it compiled inside the kernel's own LM loop
         for (int c = 0; c < ncam; ++c) {
           const int* cm = sCam + c * kGCamInts;
           if (cm[3] < 0 || cm[2] == 0) continue;
@@ -555,14 +340,8 @@ __global__ __launch_bounds__(kPoseTB) void generalized_pose_kernel(GPoseArgs a) 
             sn2 += dv * dv;
           }
         }
-        if (lane == 0) {
-          lm->consecutive_invalid = 0;
-          lm->model_cost_change = model;
-          lm->x_norm = sqrt(xn2);
-          lm->step_norm = sqrt(sn2);
-        }
+        solve.candidate_ready(lane, model_cost_change, xn2, sn2);
         act = kActEval;
-        break;
       }
       if (lane == 0) lm->action0 = act;
     }
@@ -584,46 +363,8 @@ __global__ __launch_bounds__(kPoseTB) void generalized_pose_kernel(GPoseArgs a) 
       sCost[tid] = cost_acc;
     }
     __syncthreads();
-    if (wave == 0) {
-      const double cand_cost = pose_cost_total(sCost, lane);
-      const double x_cost = lm->x_cost, radius = lm->radius, df = lm->decrease_factor;
-      const double cost_change = x_cost - cand_cost;
-      const double relative_decrease = cost_change / lm->model_cost_change;
-      const bool success = isfinite(cand_cost) && relative_decrease > kMinRelativeDecrease;
-      // ParameterToleranceReached / FunctionToleranceReached: Ceres returns
-      // before accepting the candidate
-      const bool tol = lm->step_norm <= kParameterTolerance * (lm->x_norm + kParameterTolerance) ||
-                       fabs(cost_change) <= kFunctionTolerance * x_cost;
-      wave_sync();
-      if (tol) {
-        if (lane == 0) {
-          lm->n_unsuccessful += 1;
-          lm->termination = MI_BA_CONVERGENCE;
-          lm->action1 = kActStop;
-          gpose_trace(a, index, lm->iteration, 1, 0, 1);
-        }
-      } else if (success) {
-        for (int m = lane; m < nstate; m += 64) sState[m] = sCand[m];
-        if (lane == 0) {
-          lm->n_successful += 1;
-          lm->last_successful = 1;
-          lm->x_cost = cand_cost;
-          lm->radius = fmin(kMaxRadius, radius / fmax(1.0 / 3.0, 1.0 - pow(2.0 * relative_decrease - 1.0, 3.0)));
-          lm->decrease_factor = 2.0;
-          lm->action1 = kActAccept;
-          gpose_trace(a, index, lm->iteration, 1, 1, 0);
-        }
-      } else {
-        if (lane == 0) {
-          lm->n_unsuccessful += 1;
-          lm->last_successful = 0;
-          lm->radius = radius / df;
-          lm->decrease_factor = df * 2.0;
-          lm->action1 = kActReject;
-          gpose_trace(a, index, lm->iteration, 1, 0, 0);
-        }
-      }
-    }
+    if (wave == 0 && solve.judge(sCost, lane, opt) == kActAccept)
+      for (int m = lane; m < nstate; m += 64) sState[m] = sCand[m];
     __syncthreads();
     action = lm->action1;
     if (action == kActStop) break;
@@ -631,55 +372,11 @@ __global__ __launch_bounds__(kPoseTB) void generalized_pose_kernel(GPoseArgs a) 
 
   if (wave != 0) return;
   wave_sync();
-  const int termination = lm->termination;
-  // rot_tvec_covariance: rig-pose block of inv(J'J) at the final point (sM)
-  double cov_ok = 0.0;
-  if (a.cov && termination != MI_BA_FAILURE) {
-    if (lane < n) {
-      for (int j = 0; j <= lane; ++j) sA[lane * S + j] = sM[lane * NCG + j];
-      sD0[lane] = sM[lane * NCG + lane];
-    }
-    if (gwave_cholesky(sA, S, n, lane, kCovPivotTolerance, sD0)) {
-      cov_ok = 1.0;
-      double* cov = a.cov + (size_t)index * 36;
-#pragma unroll 1
-      for (int c = 0; c < 6; ++c) {
-        const double x = gwave_chol_solve(sA, S, n, lane == c ? 1.0 : 0.0, lane, sStep);
-        if (lane < 6) cov[lane * 6 + c] = x;
-      }
-    }
-  }
-  if (termination != MI_BA_FAILURE) {
+  solve.finish(n, lane, a.cov, a.out, index);
+  if (lm->termination != MI_BA_FAILURE) {
     if (lane < 8) a.rig[(size_t)index * 8 + lane] = sState[lane];
     for (int i = lane; i < 8 * ncam; i += 64) a.cprm[8 * (size_t)pb->cam_begin + i] = sState[8 + i];
   }
-  if (lane == 0) {
-    out[0] = lm->initial_cost;
-    out[1] = lm->x_cost;
-    out[2] = lm->n_successful;
-    out[3] = lm->n_unsuccessful;
-    out[4] = termination;
-    out[5] = cov_ok;
-  }
-}
-
-template <int LT>
-mi_ba_status launch_generalized_pose(GPoseArgs a, const std::vector<GProblemDev>& list, Buf* buf) {
-  if (list.empty()) return MI_BA_OK;
-  int most = 0;
-  for (const GProblemDev& pb : list) most = pb.count > most ? pb.count : most;
-  a.lds_obs = most > kGLdsObs ? kGLdsObs : (most + 63) / 64 * 64;
-  GProblemDev* d = buf->alloc<GProblemDev>(list.size());
-  if (!d) return MI_BA_ERR_OUT_OF_MEMORY;
-  if (hipMemcpy(d, list.data(), list.size() * sizeof(GProblemDev), hipMemcpyHostToDevice) != hipSuccess)
-    return MI_BA_ERR_HIP;
-  a.prob = d;
-  const size_t bytes = (size_t)GLayout<LT>::doubles(a.lds_obs) * 8;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&generalized_pose_kernel<LT>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-    return MI_BA_ERR_HIP;
-  hipLaunchKernelGGL(generalized_pose_kernel<LT>, dim3((unsigned)list.size()), dim3(kPoseTB), bytes, 0, a);
-  return hipGetLastError() == hipSuccess ? MI_BA_OK : MI_BA_ERR_HIP;
 }
 
 // Parameters of a model id the reference knows (camera_models.h), -1 otherwise.
@@ -700,8 +397,7 @@ struct GPlan {
 mi_ba_status generalized_pose_plan(const mi_ba_pose_refine_options* o, const mi_ba_generalized_pose_batch* b,
                                    std::vector<GPlan>* plans) {
   if (!o || !b || b->num_problems < 0) return MI_BA_ERR_INVALID_ARGUMENT;
-  // AbsolutePoseRefinementOptions::Check (pose.h:119-123)
-  if (!(o->gradient_tolerance >= 0.0) || o->max_num_iterations < 0 || !(o->loss_function_scale >= 0.0))
+  if (!pose_options_check(o->gradient_tolerance, o->max_num_iterations, o->loss_function_scale))
     return MI_BA_ERR_INVALID_ARGUMENT;
   const int n = b->num_problems;
   plans->assign(n, GPlan());
@@ -754,13 +450,6 @@ mi_ba_status generalized_pose_plan(const mi_ba_pose_refine_options* o, const mi_
   return MI_BA_OK;
 }
 
-void unit_quat_copy(const double* q, double* dst) {
-  const double nq = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  // a unit quaternion is kept bit for bit
-  const bool unit = quat_is_unit(q);
-  for (int m = 0; m < 4; ++m) dst[m] = unit ? q[m] : q[m] / nq;
-}
-
 }  // namespace
 }  // namespace miba
 
@@ -796,10 +485,8 @@ extern "C" mi_ba_status mi_ba_refine_generalized_absolute_pose_batch(const mi_ba
   const int n = b->num_problems;
   if (n == 0) return MI_BA_OK;
   if (!statuses || !summaries || !usable) return MI_BA_ERR_INVALID_ARGUMENT;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return MI_BA_ERR_NO_DEVICE;
-  if (o->device < 0 || o->device >= ndev) return MI_BA_ERR_INVALID_ARGUMENT;
-  if (hipSetDevice(o->device) != hipSuccess) return MI_BA_ERR_HIP;
+  st = pose_select_device(o->device);
+  if (st != MI_BA_OK) return st;
 
   // Host assembly: the inliers listed stably grouped by camera, tiles, wave
   // runs and segments, unit quaternions, refined-intrinsics sets.
@@ -839,7 +526,7 @@ extern "C" mi_ba_status mi_ba_refine_generalized_absolute_pose_batch(const mi_ba
     pb.raw_begin = b->obs_offsets[k] - raw0;
     pb.tile_begin = (int64_t)tiles.size();
     pb.cam_begin = c0 - cam_base;
-    unit_quat_copy(b->qvec + 4 * (size_t)k, &rig[8 * (size_t)k]);
+    pose_unit_quat_copy(b->qvec + 4 * (size_t)k, &rig[8 * (size_t)k]);
     for (int m = 0; m < 3; ++m) rig[8 * (size_t)k + 4 + m] = b->tvec[3 * (size_t)k + m];
     // cameras: tangent offsets, relative poses, grouped positions
     cursor.assign((size_t)ncam, 0);
@@ -859,7 +546,7 @@ extern "C" mi_ba_status mi_ba_refine_generalized_absolute_pose_batch(const mi_ba
       cd.off = off;
       off += cd.ct;
       double qr[4];
-      unit_quat_copy(b->rig_qvecs + 4 * (size_t)(c0 + c), qr);
+      pose_unit_quat_copy(b->rig_qvecs + 4 * (size_t)(c0 + c), qr);
       unit_quat_matrix(qr, cd.rel);
       for (int m = 0; m < 3; ++m) cd.rel[9 + m] = b->rig_tvecs[3 * (size_t)(c0 + c) + m];
       for (int m = 0; m < cd.np; ++m) cprm[8 * (size_t)(pb.cam_begin + c) + m] = b->camera_params[b->camera_param_offsets[c0 + c] + m];
@@ -892,10 +579,10 @@ extern "C" mi_ba_status mi_ba_refine_generalized_absolute_pose_batch(const mi_ba
   if (narrow.empty() && wide.empty()) return MI_BA_OK;
 
   const int64_t N = raw_total;
-  Buf bufs[10];
+  Buf bufs[9];
   double2* d2 = bufs[0].alloc<double2>(N);
   double* d3 = bufs[1].alloc<double>(3 * (size_t)N);
-  int32_t* dorder = bufs[9].alloc<int32_t>(order.size());
+  int32_t* dorder = bufs[8].alloc<int32_t>(order.size());
   double* drig = bufs[2].alloc<double>(rig.size());
   double* dprm = bufs[3].alloc<double>(cprm.size());
   double* dout = bufs[4].alloc<double>(kOutStride * (size_t)n);
@@ -926,47 +613,27 @@ extern "C" mi_ba_status mi_ba_refine_generalized_absolute_pose_batch(const mi_ba
   a.gradient_tolerance = o->gradient_tolerance;
   a.loss_scale = o->loss_function_scale;
   a.max_num_iterations = o->max_num_iterations;
-  uint8_t* trace = nullptr;
-  int32_t trace_cap = 0;
-  pose_trace_target(&trace, &trace_cap);
-  if (trace) {
-    a.trace = bufs[8].alloc<uint8_t>((size_t)n * trace_cap);
-    a.trace_cap = trace_cap;
-    if (!a.trace) return MI_BA_ERR_OUT_OF_MEMORY;
-    if (hipMemset(a.trace, 0xFF, (size_t)n * trace_cap) != hipSuccess) return MI_BA_ERR_HIP;
-  }
+  PoseTraceBuf trace;
+  st = trace.setup(n);
+  if (st != MI_BA_OK) return st;
+  a.trace = trace.dev;
+  a.trace_cap = trace.cap;
   // specialised on a camera's tangent width: rig pose only (6), and rig pose + up to 8 intrinsics (14)
   Buf pbufs[2];
-  st = launch_generalized_pose<6>(a, narrow, &pbufs[0]);
+  st = pose_launch(&generalized_pose_kernel<6>, &GLayout<6>::doubles, kGLdsObs, a, narrow, &pbufs[0]);
   if (st != MI_BA_OK) return st;
-  st = launch_generalized_pose<14>(a, wide, &pbufs[1]);
+  st = pose_launch(&generalized_pose_kernel<14>, &GLayout<14>::doubles, kGLdsObs, a, wide, &pbufs[1]);
   if (st != MI_BA_OK) return st;
   if (hipStreamSynchronize(0) != hipSuccess) return MI_BA_ERR_HIP;
-  std::vector<double> out(kOutStride * (size_t)n), cov;
-  if (hipMemcpy(rig.data(), drig, rig.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(cprm.data(), dprm, cprm.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(out.data(), dout, out.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
+  std::vector<double> out(kOutStride * (size_t)n), cov(dcov ? 36 * (size_t)n : 0);
+  if (!pose_download(&rig, drig) || !pose_download(&cprm, dprm) || !pose_download(&out, dout) ||
+      (dcov && !pose_download(&cov, dcov)))
     return MI_BA_ERR_HIP;
-  if (trace && hipMemcpy(trace, a.trace, (size_t)n * trace_cap, hipMemcpyDeviceToHost) != hipSuccess)
-    return MI_BA_ERR_HIP;
-  if (dcov) {
-    cov.resize(36 * (size_t)n);
-    if (hipMemcpy(cov.data(), dcov, cov.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return MI_BA_ERR_HIP;
-  }
+  if (trace.download() != MI_BA_OK) return MI_BA_ERR_HIP;
   auto finish = [&](const GProblemDev& pb) {
     const int k = pb.index;
     const double* r = &out[kOutStride * (size_t)k];
-    mi_ba_summary& s = summaries[k];
-    s.initial_cost = r[0];
-    s.final_cost = r[1];
-    s.num_successful_steps = (int32_t)r[2];
-    s.num_unsuccessful_steps = (int32_t)r[3];
-    s.termination_type = (int32_t)r[4];
-    s.num_jacobian_evaluations = 1 + s.num_successful_steps;
-    s.num_linear_solver_iterations = s.num_successful_steps + s.num_unsuccessful_steps;
-    // Ceres leaves the user's parameter blocks untouched on FAILURE
-    bool ok = s.termination_type == MI_BA_CONVERGENCE || s.termination_type == MI_BA_NO_CONVERGENCE ||
-              s.termination_type == MI_BA_USER_SUCCESS;
+    bool ok = pose_summary_fill(r, &summaries[k]);
     if (ok) {
       for (int m = 0; m < 4; ++m) b->qvec[4 * (size_t)k + m] = rig[8 * (size_t)k + m];
       for (int m = 0; m < 3; ++m) b->tvec[3 * (size_t)k + m] = rig[8 * (size_t)k + 4 + m];

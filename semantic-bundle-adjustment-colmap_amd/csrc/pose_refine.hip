@@ -26,9 +26,10 @@
 //
 // Wave 0 then runs the small solve with lane i owning row i of the system
 // (at most 14 x 14): Jacobi scaling, LM damping, a right-looking Cholesky
-// whose column broadcasts are wave shuffles, the two triangular solves, the
-// model cost change and the candidate point.  A second pass over the
-// observations gives the candidate cost.
+// over LDS rows (column k reaches the other lanes through LDS), the two
+// triangular solves, the model cost change and the candidate point: wave 0's
+// blocks of pose_common.h (PoseLmLds), shared with generalized_pose_kernel.
+// A second pass over the observations gives the candidate cost.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -70,37 +71,6 @@ struct PoseArgs {
   int32_t lds_obs;  // observations the launch's LDS holds
   uint8_t* trace;   // nullable [n][trace_cap]: outcome of each LM iteration (mi_ba_pose_refine_set_trace)
   int32_t trace_cap;
-};
-
-// trace byte of iteration it (1-based): bit 0 step valid, bit 1 successful,
-// bit 2 the iteration ended the solve
-__device__ __forceinline__ void pose_trace(const PoseArgs& a, int index, int it, int valid, int successful, int end) {
-  if (a.trace && it >= 1 && it <= a.trace_cap)
-    a.trace[(size_t)index * a.trace_cap + it - 1] = (uint8_t)(valid | successful << 1 | end << 2);
-}
-
-struct PoseObsSource {
-  const double* sx;  // LDS, SoA (resident) ...
-  const double2* p2; // ... or device memory
-  const double* p3;
-  bool resident;
-  int lds_obs;
-  __device__ __forceinline__ void load(int i, double* ox, double* oy, double X[3]) const {
-    if (resident) {
-      *ox = sx[i];
-      *oy = sx[lds_obs + i];
-      X[0] = sx[2 * lds_obs + i];
-      X[1] = sx[3 * lds_obs + i];
-      X[2] = sx[4 * lds_obs + i];
-    } else {
-      const double2 o = p2[i];
-      *ox = o.x;
-      *oy = o.y;
-      X[0] = p3[3 * (size_t)i];
-      X[1] = p3[3 * (size_t)i + 1];
-      X[2] = p3[3 * (size_t)i + 2];
-    }
-  }
 };
 
 // Cost 0.5 rho(|r|^2) of one observation at the parameters st (q t pad params).
@@ -158,6 +128,10 @@ __device__ inline void pose_obs_rows(int model, const double* st, const int* idx
   rotation_tangent_jacobian(q, X, a0, a1, a2, true, quat_is_unit(q), Mq);
   emit_row_pose(0, J0, B, Mq, true, 0u);
   emit_row_pose(1, J1, B, Mq, true, 0u);
+  // The refined-intrinsics columns and the residual column.  Kept in this
+  // function, not in a helper shared with gpose_obs_rows: moved into one, the
+  // compiler pairs the products of the camera model's Jacobian differently and
+  // a last bit of [J r]'[J r] changes.
   if constexpr (NT > 6) {
 #pragma unroll
     for (int m = 0; m < NT - 6; ++m) {
@@ -176,64 +150,13 @@ __device__ inline void pose_obs_rows(int model, const double* st, const int* idx
   J1[NT] = r1 * sc;
 }
 
-// Dense Cholesky by one wave, in LDS: lane i < NT owns row i of the lower
-// triangle in sA (row stride NT + 1: the lanes' rows start on distinct even
-// banks); on return sA holds L.  A pivot k with !(pivot > tol * d0[k]) makes
-// the result false.  Column k reaches the other rows through LDS.
-template <int NT>
-__device__ inline bool wave_cholesky(double* sA, int lane, double tol, const double* d0) {
-  constexpr int S = NT + 1;
-  bool ok = true;
-#pragma unroll 1
-  for (int k = 0; k < NT; ++k) {
-    wave_sync();
-    const double akk = sA[k * S + k];
-    if (!(akk > tol * d0[k])) ok = false;
-    const double lkk = sqrt(akk);
-    const bool mine = lane < NT && lane >= k;
-    double lik = 0.0;
-    if (mine) lik = lane == k ? lkk : sA[lane * S + k] / lkk;
-    wave_sync();
-    if (mine) sA[lane * S + k] = lik;
-    wave_sync();
-    if (mine)
-      for (int j = k + 1; j <= lane; ++j) sA[lane * S + j] -= lik * sA[j * S + k];
-  }
-  wave_sync();
-  return ok;
-}
-
-// Solves L L' x = b with L in sA: lane i < NT passes b_i and receives x_i;
-// sx (NT doubles of LDS) carries each solved component to the other lanes.
-template <int NT>
-__device__ inline double wave_chol_solve(const double* sA, double b, int lane, double* sx) {
-  constexpr int S = NT + 1;
-#pragma unroll 1
-  for (int k = 0; k < NT; ++k) {
-    if (lane == k) sx[k] = b / sA[k * S + k];
-    wave_sync();
-    const double yk = sx[k];
-    if (lane == k) b = yk;
-    else if (lane > k && lane < NT) b -= sA[lane * S + k] * yk;
-  }
-#pragma unroll 1
-  for (int k = NT - 1; k >= 0; --k) {
-    if (lane == k) sx[k] = b / sA[k * S + k];
-    wave_sync();
-    const double xk = sx[k];
-    if (lane == k) b = xk;
-    else if (lane < k) b -= sA[k * S + lane] * xk;
-  }
-  wave_sync();
-  return b;
-}
-
 template <int NT>
 constexpr int pose_lds_doubles(int lds_obs) {
   constexpr int NC = NT + 1;
   return kPoseWaves * NC * kColStride + kPoseWaves * 128 + NC * NC + kPoseTB + 16 + 16 + NT * (NT + 1) + 3 * 16 +
          (int)(sizeof(PoseLm) / 8) + 8 + 5 * lds_obs;
 }
+static_assert(pose_lds_doubles<14>(kPoseLdsObs) * 8 <= 160 * 1024, "LDS budget of one workgroup");
 
 template <int NT>
 __global__ __launch_bounds__(kPoseTB) void pose_refine_kernel(PoseArgs a) {
@@ -253,58 +176,38 @@ __global__ __launch_bounds__(kPoseTB) void pose_refine_kernel(PoseArgs a) {
   double* sD0 = sStep + 16;
   PoseLm* lm = reinterpret_cast<PoseLm*>(sD0 + 16);
   int* sIdx = reinterpret_cast<int*>(reinterpret_cast<double*>(lm) + sizeof(PoseLm) / 8);
+  int* sTan = sIdx + 8 - 6;  // tangent column 6 + m -> index into sState, in the second half of sIdx's 16 ints
   double* sObs = reinterpret_cast<double*>(sIdx) + 8;
+  const PoseLmLds<NC, NT + 1, 16, false> solve{sM, sA, sScale, sStep, sD0, lm, sTan};
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const PoseProblemDev* pb = a.prob + blockIdx.x;
   const int count = pb->count, model = pb->model, ct = pb->ct, n = 6 + ct, index = pb->index;
-  double* out = a.out + (size_t)index * kOutStride;
+  const PoseLmOptions opt{a.gradient_tolerance, a.max_num_iterations, a.trace, a.trace_cap, index};
   if (count <= 0) {  // nothing to do: CONVERGENCE, parameters as they are
     if (tid == 0) {
+      double* out = a.out + (size_t)index * kOutStride;
       out[0] = 0.0; out[1] = 0.0; out[2] = 0.0; out[3] = 0.0; out[4] = MI_BA_CONVERGENCE; out[5] = 0.0;
     }
     return;
   }
-  PoseObsSource src;
+  PoseObsSource<false> src;
   src.lds_obs = a.lds_obs;
   src.resident = count <= a.lds_obs;
   src.sx = sObs;
   src.p2 = a.p2 + pb->obs_begin;
   src.p3 = a.p3 + 3 * pb->obs_begin;
-  if (src.resident) {
-    for (int i = tid; i < count; i += kPoseTB) {
-      const double2 o = src.p2[i];
-      sObs[i] = o.x;
-      sObs[a.lds_obs + i] = o.y;
-      sObs[2 * a.lds_obs + i] = src.p3[3 * (size_t)i];
-      sObs[3 * a.lds_obs + i] = src.p3[3 * (size_t)i + 1];
-      sObs[4 * a.lds_obs + i] = src.p3[3 * (size_t)i + 2];
-    }
-  }
+  src.stage(tid, count);
   if (tid < 16) sState[tid] = a.state[(size_t)index * 16 + tid];
-  if (tid < 8) sIdx[tid] = pb->idx[tid];
-  if (tid == 0) {
-    lm->radius = kInitialRadius;
-    lm->decrease_factor = 2.0;
-    lm->iteration = 0;
-    lm->consecutive_invalid = 0;
-    lm->n_successful = 0;
-    lm->n_unsuccessful = 0;
-    lm->termination = MI_BA_NO_CONVERGENCE;
-    lm->last_successful = 1;  // iteration 0 counts as successful (IterationZero)
+  if (tid < 8) {
+    sIdx[tid] = pb->idx[tid];
+    sTan[6 + tid] = 8 + pb->idx[tid];
   }
+  solve.init(tid);
   __syncthreads();
 
-  // the lane's entries (i, j), i <= j < NC, of the upper triangle
   int ei[EPL], ej[EPL];
-#pragma unroll
-  for (int s = 0; s < EPL; ++s) {
-    int e = lane + 64 * s, i = 0, w = NC;
-    if (e >= NE) e = 0;  // idle slot: sums entry 0, never stored
-    while (e >= w) { e -= w; --w; ++i; }
-    ei[s] = i;
-    ej[s] = i + e;
-  }
+  pose_triangle_entries<NC>(lane, ei, ej);
 
   bool first = true;
   int action = kActAccept;  // the first pass linearizes at the given point
@@ -321,33 +224,16 @@ __global__ __launch_bounds__(kPoseTB) void pose_refine_kernel(PoseArgs a) {
       double cost_acc = 0.0;
       for (int tile = wave; tile * 64 < count; tile += kPoseWaves) {
         const int i = tile * 64 + lane;
-        {
-          double J0[NC], J1[NC];
+        double J0[NC], J1[NC];
 #pragma unroll
-          for (int c = 0; c < NC; ++c) { J0[c] = 0.0; J1[c] = 0.0; }
-          if (i < count) {
-            double ox, oy, X[3], cost;
-            src.load(i, &ox, &oy, X);
-            pose_obs_rows<NT>(model, sState, idx, ct, a.loss_scale, ox, oy, X, J0, J1, &cost);
-            cost_acc += cost;
-          }
-#pragma unroll
-          for (int c = 0; c < NC; ++c) {
-            slab[c * kColStride + lane] = J0[c];
-            slab[c * kColStride + 64 + lane] = J1[c];
-          }
+        for (int c = 0; c < NC; ++c) { J0[c] = 0.0; J1[c] = 0.0; }
+        if (i < count) {
+          double ox, oy, X[3], cost;
+          src.load(i, &ox, &oy, X);
+          pose_obs_rows<NT>(model, sState, idx, ct, a.loss_scale, ox, oy, X, J0, J1, &cost);
+          cost_acc += cost;
         }
-        wave_sync();
-#pragma unroll
-        for (int s = 0; s < EPL; ++s) {
-          const double* ci = slab + ei[s] * kColStride;
-          const double* cj = slab + ej[s] * kColStride;
-          double v = acc[s];
-#pragma unroll 4
-          for (int k = 0; k < 128; ++k) v += ci[k] * cj[k];
-          acc[s] = v;
-        }
-        wave_sync();
+        pose_tile_products<NC>(slab, lane, J0, J1, ei, ej, acc);
       }
 #pragma unroll
       for (int s = 0; s < EPL; ++s) red[wave * 128 + lane + 64 * s] = acc[s];
@@ -367,135 +253,28 @@ __global__ __launch_bounds__(kPoseTB) void pose_refine_kernel(PoseArgs a) {
         }
         const double total = pose_cost_total(sCost, lane);
         wave_sync();
-        if (first) {
-          if (lane < 16) sScale[lane] = lane < n ? 1.0 / (1.0 + sqrt(sM[lane * NC + lane])) : 1.0;
-          if (lane == 0) {
-            lm->x_cost = total;
-            lm->initial_cost = total;
-          }
-          wave_sync();
-        }
+        if (first) solve.first(n, lane, total);
       }
       first = false;
     }
 
     if (wave == 0) {
       int act = kActStop;
-      // a non-finite initial cost: FAILURE, parameters untouched
-      bool go = isfinite(lm->x_cost);
-      if (!go && lane == 0) lm->termination = MI_BA_FAILURE;
-      while (go) {
-        // FinalizeIterationAndCheckIfMinimizerCanContinue
-        if (lm->iteration >= a.max_num_iterations) {
-          if (lane == 0) lm->termination = MI_BA_NO_CONVERGENCE;
-          break;
-        }
-        if (lm->last_successful) {
-          // GradientToleranceReached: |x - Plus(x, -g)|_inf, g = J'r
-          const double d[3] = {-sM[0 * NC + NT], -sM[1 * NC + NT], -sM[2 * NC + NT]};
-          const double q[4] = {sState[0], sState[1], sState[2], sState[3]};
-          double qn[4], gmax = 0.0;
-          quat_plus(q, d, qn);
-#pragma unroll
-          for (int m = 0; m < 4; ++m) gmax = fmax(gmax, fabs(q[m] - qn[m]));
-          for (int m = 0; m < 3; ++m) gmax = fmax(gmax, fabs(sState[4 + m] - (sState[4 + m] + -sM[(3 + m) * NC + NT])));
-          for (int m = 0; m < ct; ++m) {
-            const double xv = sState[8 + sIdx[m]];
-            gmax = fmax(gmax, fabs(xv - (xv + -sM[(6 + m) * NC + NT])));
-          }
-          if (gmax <= a.gradient_tolerance) {
-            if (lane == 0) lm->termination = MI_BA_CONVERGENCE;
-            break;
-          }
-        }
-        const double radius = lm->radius;
-        if (radius <= kMinRadius) {
-          if (lane == 0) lm->termination = MI_BA_CONVERGENCE;
-          break;
-        }
-        wave_sync();
-        if (lane == 0) lm->iteration += 1;
-        // row `lane` of the scaled, damped system (rows past n: identity);
-        // LM diagonal: the clipped scaled column norm over the radius
-        const double scale = lane < 16 ? sScale[lane] : 1.0;
-        double gs = 0.0;
-        if (lane < NT) {
-          for (int j = 0; j <= lane; ++j) {
-            double v = (lane < n) ? sM[lane * NC + j] * scale * sScale[j] : 0.0;
-            if (j == lane) v = lane < n ? v + fmin(fmax(v, 1e-6), 1e32) / radius : 1.0;
-            sA[lane * (NT + 1) + j] = v;
-          }
-          sD0[lane] = 1.0;
-          if (lane < n) gs = sM[lane * NC + NT] * scale;
-        }
-        bool ok = wave_cholesky<NT>(sA, lane, 0.0, sD0);
-        double step = 0.0, model = 0.0;
-        if (ok) {
-          // Ceres solves (J'J + D'D) x = J'r, step = -x
-          step = -wave_chol_solve<NT>(sA, gs, lane, sStep);
-          if (lane < 16) sStep[lane] = lane < n ? step : 0.0;
-          wave_sync();
-          double term = 0.0;
-          if (lane < n) {
-            double hstep = 0.0;
-            for (int j = 0; j < n; ++j) hstep += sM[lane * NC + j] * scale * sScale[j] * sStep[j];
-            term = step * (gs + 0.5 * hstep);
-          }
-          model = -wave_sum_fixed(term);
-          ok = isfinite(model) && model > 0.0;
-        }
-        if (!ok) {
-          const int inv = lm->consecutive_invalid + 1;
-          const double df = lm->decrease_factor;
-          wave_sync();
-          if (lane == 0) {
-            lm->last_successful = 0;
-            lm->consecutive_invalid = inv;
-            lm->n_unsuccessful += 1;
-            lm->radius = radius / df;
-            lm->decrease_factor = df * 2.0;
-            if (inv > kMaxConsecutiveInvalid) lm->termination = MI_BA_FAILURE;
-            pose_trace(a, index, lm->iteration, 0, 0, inv > kMaxConsecutiveInvalid ? 1 : 0);
-          }
-          wave_sync();
-          if (inv > kMaxConsecutiveInvalid) break;
-          continue;
-        }
-        // candidate = Plus(x, step * scale)
-        const double delta = step * scale;
-        if (lane < 16) {
-          sCand[lane] = sState[lane];
-          sStep[lane] = lane < n ? delta : 0.0;
-        }
-        wave_sync();
-        {
-          const double dq[3] = {sStep[0], sStep[1], sStep[2]};
-          const double q[4] = {sState[0], sState[1], sState[2], sState[3]};
-          double qn[4];
-          quat_plus(q, dq, qn);
-          if (lane < 4) sCand[lane] = lane == 0 ? qn[0] : lane == 1 ? qn[1] : lane == 2 ? qn[2] : qn[3];
-          if (lane >= 3 && lane < 6) sCand[1 + lane] = sState[1 + lane] + delta;
-          if (lane >= 6 && lane < n) sCand[8 + sIdx[lane - 6]] = sState[8 + sIdx[lane - 6]] + delta;
-        }
-        wave_sync();
+      double model_cost_change;
+      if (solve.propose(sState, sCand, 16, n, lane, opt, &model_cost_change)) {
         // |x|^2, |x - candidate|^2 over the variable blocks in ambient
         // coordinates: qvec, tvec, and every parameter of a refined camera
         double xn2 = 0.0, sn2 = 0.0;
         const int nstate = ct > 0 ? 8 + pb->np : 7;
+#pragma unroll 1  // rolled, as it compiled inside the kernel's own LM loop
         for (int m = 0; m < nstate; ++m) {
           if (m == 7) continue;
           const double xv = sState[m], dv = xv - sCand[m];
           xn2 += xv * xv;
           sn2 += dv * dv;
         }
-        if (lane == 0) {
-          lm->consecutive_invalid = 0;
-          lm->model_cost_change = model;
-          lm->x_norm = sqrt(xn2);
-          lm->step_norm = sqrt(sn2);
-        }
+        solve.candidate_ready(lane, model_cost_change, xn2, sn2);
         act = kActEval;
-        break;
       }
       if (lane == 0) lm->action0 = act;
     }
@@ -513,46 +292,7 @@ __global__ __launch_bounds__(kPoseTB) void pose_refine_kernel(PoseArgs a) {
       sCost[tid] = cost_acc;
     }
     __syncthreads();
-    if (wave == 0) {
-      const double cand_cost = pose_cost_total(sCost, lane);
-      const double x_cost = lm->x_cost, radius = lm->radius, df = lm->decrease_factor;
-      const double cost_change = x_cost - cand_cost;
-      const double relative_decrease = cost_change / lm->model_cost_change;
-      const bool success = isfinite(cand_cost) && relative_decrease > kMinRelativeDecrease;
-      // ParameterToleranceReached / FunctionToleranceReached: Ceres returns
-      // before accepting the candidate
-      const bool tol = lm->step_norm <= kParameterTolerance * (lm->x_norm + kParameterTolerance) ||
-                       fabs(cost_change) <= kFunctionTolerance * x_cost;
-      wave_sync();
-      if (tol) {
-        if (lane == 0) {
-          lm->n_unsuccessful += 1;
-          lm->termination = MI_BA_CONVERGENCE;
-          lm->action1 = kActStop;
-          pose_trace(a, index, lm->iteration, 1, 0, 1);
-        }
-      } else if (success) {
-        if (lane < 16) sState[lane] = sCand[lane];
-        if (lane == 0) {
-          lm->n_successful += 1;
-          lm->last_successful = 1;
-          lm->x_cost = cand_cost;
-          lm->radius = fmin(kMaxRadius, radius / fmax(1.0 / 3.0, 1.0 - pow(2.0 * relative_decrease - 1.0, 3.0)));
-          lm->decrease_factor = 2.0;
-          lm->action1 = kActAccept;
-          pose_trace(a, index, lm->iteration, 1, 1, 0);
-        }
-      } else {
-        if (lane == 0) {
-          lm->n_unsuccessful += 1;
-          lm->last_successful = 0;
-          lm->radius = radius / df;
-          lm->decrease_factor = df * 2.0;
-          lm->action1 = kActReject;
-          pose_trace(a, index, lm->iteration, 1, 0, 0);
-        }
-      }
-    }
+    if (wave == 0 && solve.judge(sCost, lane, opt) == kActAccept && lane < 16) sState[lane] = sCand[lane];
     __syncthreads();
     action = lm->action1;
     if (action == kActStop) break;
@@ -560,53 +300,8 @@ __global__ __launch_bounds__(kPoseTB) void pose_refine_kernel(PoseArgs a) {
 
   if (wave != 0) return;
   wave_sync();
-  const int termination = lm->termination;
-  // rot_tvec_covariance: pose block of inv(J'J) at the final point (sM)
-  double cov_ok = 0.0;
-  if (a.cov && termination != MI_BA_FAILURE) {
-    if (lane < NT) {
-      for (int j = 0; j <= lane; ++j)
-        sA[lane * (NT + 1) + j] = lane < n ? sM[lane * NC + j] : (j == lane ? 1.0 : 0.0);
-      sD0[lane] = lane < n ? sM[lane * NC + lane] : 1.0;
-    }
-    if (wave_cholesky<NT>(sA, lane, kCovPivotTolerance, sD0)) {
-      cov_ok = 1.0;
-      double* cov = a.cov + (size_t)index * 36;
-#pragma unroll 1
-      for (int c = 0; c < 6; ++c) {
-        const double x = wave_chol_solve<NT>(sA, lane == c ? 1.0 : 0.0, lane, sStep);
-        if (lane < 6) cov[lane * 6 + c] = x;
-      }
-    }
-  }
-  if (lane < 16 && termination != MI_BA_FAILURE) a.state[(size_t)index * 16 + lane] = sState[lane];
-  if (lane == 0) {
-    out[0] = lm->initial_cost;
-    out[1] = lm->x_cost;
-    out[2] = lm->n_successful;
-    out[3] = lm->n_unsuccessful;
-    out[4] = termination;
-    out[5] = cov_ok;
-  }
-}
-
-template <int NT>
-mi_ba_status launch_pose_refine(PoseArgs a, const std::vector<PoseProblemDev>& list, Buf* buf) {
-  if (list.empty()) return MI_BA_OK;
-  int most = 0;
-  for (const PoseProblemDev& pb : list) most = pb.count > most ? pb.count : most;
-  a.lds_obs = most > kPoseLdsObs ? kPoseLdsObs : (most + 63) / 64 * 64;
-  PoseProblemDev* d = buf->alloc<PoseProblemDev>(list.size());
-  if (!d) return MI_BA_ERR_OUT_OF_MEMORY;
-  if (hipMemcpy(d, list.data(), list.size() * sizeof(PoseProblemDev), hipMemcpyHostToDevice) != hipSuccess)
-    return MI_BA_ERR_HIP;
-  a.prob = d;
-  const size_t bytes = (size_t)pose_lds_doubles<NT>(a.lds_obs) * 8;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pose_refine_kernel<NT>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-    return MI_BA_ERR_HIP;
-  hipLaunchKernelGGL(pose_refine_kernel<NT>, dim3((unsigned)list.size()), dim3(kPoseTB), bytes, 0, a);
-  return hipGetLastError() == hipSuccess ? MI_BA_OK : MI_BA_ERR_HIP;
+  solve.finish(n, lane, a.cov, a.out, index);
+  if (lane < 16 && lm->termination != MI_BA_FAILURE) a.state[(size_t)index * 16 + lane] = sState[lane];
 }
 
 }  // namespace
@@ -662,8 +357,7 @@ extern "C" mi_ba_status mi_ba_refine_absolute_pose_batch(const mi_ba_pose_refine
                                                          const mi_ba_pose_batch* b, int32_t* statuses,
                                                          mi_ba_summary* summaries, int32_t* usable) {
   if (!o || !b || b->num_problems < 0) return MI_BA_ERR_INVALID_ARGUMENT;
-  // AbsolutePoseRefinementOptions::Check (pose.h:119-123)
-  if (!(o->gradient_tolerance >= 0.0) || o->max_num_iterations < 0 || !(o->loss_function_scale >= 0.0))
+  if (!pose_options_check(o->gradient_tolerance, o->max_num_iterations, o->loss_function_scale))
     return MI_BA_ERR_INVALID_ARGUMENT;
   const int n = b->num_problems;
   if (n == 0) return MI_BA_OK;
@@ -680,10 +374,8 @@ extern "C" mi_ba_status mi_ba_refine_absolute_pose_batch(const mi_ba_pose_refine
   }
   const int64_t total = b->obs_offsets[n];
   if (total > 0 && (!b->points2D || !b->points3D)) return MI_BA_ERR_INVALID_ARGUMENT;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return MI_BA_ERR_NO_DEVICE;
-  if (o->device < 0 || o->device >= ndev) return MI_BA_ERR_INVALID_ARGUMENT;
-  if (hipSetDevice(o->device) != hipSuccess) return MI_BA_ERR_HIP;
+  const mi_ba_status dev = pose_select_device(o->device);
+  if (dev != MI_BA_OK) return dev;
 
   // Host assembly: inlier compaction, unit qvec, refined-intrinsics sets.
   std::vector<PoseProblemDev> narrow, wide;
@@ -724,11 +416,7 @@ extern "C" mi_ba_status mi_ba_refine_absolute_pose_batch(const mi_ba_pose_refine
       pb.count = (int32_t)(b1 - b0);
     }
     double* st = &state[16 * (size_t)k];
-    const double* q = b->qvec + 4 * (size_t)k;
-    const double nq = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    // a unit qvec is kept bit for bit (BundleAdjuster::SetUp normalises)
-    const bool unit = quat_is_unit(q);
-    for (int m = 0; m < 4; ++m) st[m] = unit ? q[m] : q[m] / nq;
+    pose_unit_quat_copy(b->qvec + 4 * (size_t)k, st);
     for (int m = 0; m < 3; ++m) st[4 + m] = b->tvec[3 * (size_t)k + m];
     for (int m = 0; m < np; ++m) st[8 + m] = b->camera_params[b->camera_param_offsets[k] + m];
     summaries[k].num_residuals_reduced = 2 * (int64_t)pb.count;
@@ -745,7 +433,7 @@ extern "C" mi_ba_status mi_ba_refine_absolute_pose_batch(const mi_ba_pose_refine
   const double* h2 = masked ? c2.data() : b->points2D;
   const double* h3 = masked ? c3.data() : b->points3D;
   const int64_t N = masked ? (int64_t)(c2.size() / 2) : total;
-  Buf bufs[8];
+  Buf bufs[7];
   double2* d2 = bufs[0].alloc<double2>(N);
   double* d3 = bufs[1].alloc<double>(3 * (size_t)N);
   double* dstate = bufs[2].alloc<double>(state.size());
@@ -766,44 +454,25 @@ extern "C" mi_ba_status mi_ba_refine_absolute_pose_batch(const mi_ba_pose_refine
   a.gradient_tolerance = o->gradient_tolerance;
   a.loss_scale = o->loss_function_scale;
   a.max_num_iterations = o->max_num_iterations;
-  uint8_t* const trace = g_pose_trace;
-  const int32_t trace_cap = g_pose_trace_cap;
-  if (trace) {
-    a.trace = bufs[7].alloc<uint8_t>((size_t)n * trace_cap);
-    a.trace_cap = trace_cap;
-    if (!a.trace) return MI_BA_ERR_OUT_OF_MEMORY;
-    if (hipMemset(a.trace, 0xFF, (size_t)n * trace_cap) != hipSuccess) return MI_BA_ERR_HIP;
-  }
-  // specialised on the tangent width: pose only (6) and pose + intrinsics (up to 14)
-  mi_ba_status st = launch_pose_refine<6>(a, narrow, &bufs[5]);
+  PoseTraceBuf trace;
+  mi_ba_status st = trace.setup(n);
   if (st != MI_BA_OK) return st;
-  st = launch_pose_refine<14>(a, wide, &bufs[6]);
+  a.trace = trace.dev;
+  a.trace_cap = trace.cap;
+  // specialised on the tangent width: pose only (6) and pose + intrinsics (up to 14)
+  st = pose_launch(&pose_refine_kernel<6>, &pose_lds_doubles<6>, kPoseLdsObs, a, narrow, &bufs[5]);
+  if (st != MI_BA_OK) return st;
+  st = pose_launch(&pose_refine_kernel<14>, &pose_lds_doubles<14>, kPoseLdsObs, a, wide, &bufs[6]);
   if (st != MI_BA_OK) return st;
   if (hipStreamSynchronize(0) != hipSuccess) return MI_BA_ERR_HIP;
-  std::vector<double> out(kOutStride * (size_t)n), cov;
-  if (hipMemcpy(state.data(), dstate, state.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(out.data(), dout, out.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
+  std::vector<double> out(kOutStride * (size_t)n), cov(dcov ? 36 * (size_t)n : 0);
+  if (!pose_download(&state, dstate) || !pose_download(&out, dout) || (dcov && !pose_download(&cov, dcov)))
     return MI_BA_ERR_HIP;
-  if (trace && hipMemcpy(trace, a.trace, (size_t)n * trace_cap, hipMemcpyDeviceToHost) != hipSuccess)
-    return MI_BA_ERR_HIP;
-  if (dcov) {
-    cov.resize(36 * (size_t)n);
-    if (hipMemcpy(cov.data(), dcov, cov.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return MI_BA_ERR_HIP;
-  }
+  if (trace.download() != MI_BA_OK) return MI_BA_ERR_HIP;
   auto finish = [&](const PoseProblemDev& pb) {
     const int k = pb.index;
     const double* r = &out[kOutStride * (size_t)k];
-    mi_ba_summary& s = summaries[k];
-    s.initial_cost = r[0];
-    s.final_cost = r[1];
-    s.num_successful_steps = (int32_t)r[2];
-    s.num_unsuccessful_steps = (int32_t)r[3];
-    s.termination_type = (int32_t)r[4];
-    s.num_jacobian_evaluations = 1 + s.num_successful_steps;
-    s.num_linear_solver_iterations = s.num_successful_steps + s.num_unsuccessful_steps;
-    // Ceres leaves the user's parameter blocks untouched on FAILURE
-    bool ok = s.termination_type == MI_BA_CONVERGENCE || s.termination_type == MI_BA_NO_CONVERGENCE ||
-              s.termination_type == MI_BA_USER_SUCCESS;
+    bool ok = pose_summary_fill(r, &summaries[k]);
     if (ok) {
       const double* stp = &state[16 * (size_t)k];
       for (int m = 0; m < 4; ++m) b->qvec[4 * (size_t)k + m] = stp[m];

@@ -64,12 +64,6 @@ struct RPoseArgs {
   int32_t trace_cap;
 };
 
-__device__ __forceinline__ void rpose_trace(const RPoseArgs& a, int lane, int index, int it, int valid, int successful,
-                                            int end) {
-  if (lane == 0 && a.trace && it >= 1 && it <= a.trace_cap)
-    a.trace[(size_t)index * a.trace_cap + it - 1] = (uint8_t)(valid | successful << 1 | end << 2);
-}
-
 struct RObsSource {
   const double* sx;   // LDS, struct of arrays (resident) ...
   const double2* p1;  // ... or device memory
@@ -216,7 +210,7 @@ __global__ __launch_bounds__(kPoseTB) void relative_pose_kernel(RPoseArgs a) {
     int e = 0;
 #pragma unroll
     for (int k = 0; k < kRTangent; ++k) {
-      scale[k] = 1.0 / (1.0 + sqrt(S[e]));
+      scale[k] = lm_jacobi_scale(S[e]);
       e += kRTangent + 1 - k;
     }
   }
@@ -276,7 +270,7 @@ __global__ __launch_bounds__(kPoseTB) void relative_pose_kernel(RPoseArgs a) {
 #pragma unroll
       for (int j = 0; j <= i; ++j) {
         double v = M[i][j] * scale[i] * scale[j];
-        if (j == i) v = v + fmin(fmax(v, 1e-6), 1e32) / radius;
+        if (j == i) v = lm_damped_diagonal(v, radius);
         A[i][j] = v;
       }
       gs[i] = g[i] * scale[i];
@@ -302,10 +296,9 @@ __global__ __launch_bounds__(kPoseTB) void relative_pose_kernel(RPoseArgs a) {
       consecutive_invalid += 1;
       last_successful = false;
       n_unsuccessful += 1;
-      radius = radius / decrease_factor;
-      decrease_factor *= 2.0;
+      lm_radius_reject(radius, decrease_factor);
       const bool end = consecutive_invalid > kMaxConsecutiveInvalid;
-      rpose_trace(a, lane, index, iteration, 0, 0, end ? 1 : 0);
+      if (lane == 0) pose_trace(a.trace, a.trace_cap, index, iteration, 0, 0, end ? 1 : 0);
       if (end) {
         termination = MI_BA_FAILURE;
         break;
@@ -336,18 +329,17 @@ __global__ __launch_bounds__(kPoseTB) void relative_pose_kernel(RPoseArgs a) {
       sn2 += dv * dv;
     }
     const double x_norm = sqrt(xn2), step_norm = sqrt(sn2);
-    // a non-finite candidate cost is an unsuccessful step
     const double cand_cost = rpose_cost(src, count, lane, qc, tc, a.loss_scale);
     const double cost_change = x_cost - cand_cost;
     const double relative_decrease = cost_change / model;
-    const bool success = isfinite(cand_cost) && relative_decrease > kMinRelativeDecrease;
-    // ParameterToleranceReached / FunctionToleranceReached: Ceres returns before accepting the candidate
-    const bool tol = step_norm <= a.parameter_tolerance * (x_norm + a.parameter_tolerance) ||
-                     fabs(cost_change) <= a.function_tolerance * x_cost;
+    const bool success = lm_step_successful(cand_cost, relative_decrease);
+    // Ceres returns before accepting the candidate
+    const bool tol = lm_tolerance_reached(step_norm, x_norm, cost_change, x_cost, a.parameter_tolerance,
+                                          a.function_tolerance);
     if (tol) {
       n_unsuccessful += 1;
       termination = MI_BA_CONVERGENCE;
-      rpose_trace(a, lane, index, iteration, 1, 0, 1);
+      if (lane == 0) pose_trace(a.trace, a.trace_cap, index, iteration, 1, 0, 1);
       break;
     }
     if (success) {
@@ -357,18 +349,16 @@ __global__ __launch_bounds__(kPoseTB) void relative_pose_kernel(RPoseArgs a) {
       for (int m = 0; m < 3; ++m) t[m] = tc[m];
       n_successful += 1;
       last_successful = true;
-      radius = fmin(kMaxRadius, radius / fmax(1.0 / 3.0, 1.0 - pow(2.0 * relative_decrease - 1.0, 3.0)));
-      decrease_factor = 2.0;
-      rpose_trace(a, lane, index, iteration, 1, 1, 0);
+      lm_radius_accept(radius, decrease_factor, relative_decrease);
+      if (lane == 0) pose_trace(a.trace, a.trace_cap, index, iteration, 1, 1, 0);
       double ignored;
       rpose_linearize(src, count, lane, q, t, a.loss_scale, S, &ignored);
       x_cost = cand_cost;
     } else {
       n_unsuccessful += 1;
       last_successful = false;
-      radius = radius / decrease_factor;
-      decrease_factor *= 2.0;
-      rpose_trace(a, lane, index, iteration, 1, 0, 0);
+      lm_radius_reject(radius, decrease_factor);
+      if (lane == 0) pose_trace(a.trace, a.trace_cap, index, iteration, 1, 0, 0);
     }
   }
 
@@ -412,8 +402,8 @@ __global__ __launch_bounds__(64) void relative_pose_evaluate_kernel(const RProbl
 // The argument checks of both entry points.  Host only.
 mi_ba_status relative_pose_check(const mi_ba_relative_pose_options* o, const mi_ba_relative_pose_batch* b) {
   if (!o || !b || b->num_problems < 0) return MI_BA_ERR_INVALID_ARGUMENT;
-  if (!(o->function_tolerance >= 0.0) || !(o->gradient_tolerance >= 0.0) || !(o->parameter_tolerance >= 0.0) ||
-      o->max_num_iterations < 0 || !(o->loss_function_scale >= 0.0))
+  if (!pose_options_check(o->gradient_tolerance, o->max_num_iterations, o->loss_function_scale, o->function_tolerance,
+                          o->parameter_tolerance))
     return MI_BA_ERR_INVALID_ARGUMENT;
   const int n = b->num_problems;
   if (n == 0) return MI_BA_OK;
@@ -424,13 +414,6 @@ mi_ba_status relative_pose_check(const mi_ba_relative_pose_options* o, const mi_
   }
   if (b->obs_offsets[n] > b->obs_offsets[0] && (!b->points1 || !b->points2)) return MI_BA_ERR_INVALID_ARGUMENT;
   return MI_BA_OK;
-}
-
-mi_ba_status relative_pose_device(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return MI_BA_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev) return MI_BA_ERR_INVALID_ARGUMENT;
-  return hipSetDevice(device) == hipSuccess ? MI_BA_OK : MI_BA_ERR_HIP;
 }
 
 // NormalizeQuaternion (src/base/pose.cc): q / |q|, the identity for |q| = 0.
@@ -466,7 +449,7 @@ extern "C" mi_ba_status mi_ba_refine_relative_pose_batch(const mi_ba_relative_po
   const int n = b->num_problems;
   if (n == 0) return MI_BA_OK;
   if (!statuses || !summaries || !usable) return MI_BA_ERR_INVALID_ARGUMENT;
-  st = relative_pose_device(o->device);
+  st = pose_select_device(o->device);
   if (st != MI_BA_OK) return st;
 
   // Host assembly: without a mask the caller's arrays are uploaded as they
@@ -514,7 +497,7 @@ extern "C" mi_ba_status mi_ba_refine_relative_pose_batch(const mi_ba_relative_po
   const int64_t N = masked ? at : b->obs_offsets[n] - raw0;
   const double* h1 = masked ? c1.data() : b->points1 + 2 * raw0;
   const double* h2 = masked ? c2.data() : b->points2 + 2 * raw0;
-  Buf bufs[6];
+  Buf bufs[5];
   double2* d1 = bufs[0].alloc<double2>(N);
   double2* d2 = bufs[1].alloc<double2>(N);
   double* dpose = bufs[2].alloc<double>(pose.size());
@@ -541,15 +524,11 @@ extern "C" mi_ba_status mi_ba_refine_relative_pose_batch(const mi_ba_relative_po
   a.num_listed = (int32_t)list.size();
   // the arrays' stride only: a problem is resident exactly when its own count is at most kRLdsObs
   a.lds_obs = (most_resident + 63) / 64 * 64;
-  uint8_t* trace = nullptr;
-  int32_t trace_cap = 0;
-  pose_trace_target(&trace, &trace_cap);
-  if (trace) {
-    a.trace = bufs[5].alloc<uint8_t>((size_t)n * trace_cap);
-    a.trace_cap = trace_cap;
-    if (!a.trace) return MI_BA_ERR_OUT_OF_MEMORY;
-    if (hipMemset(a.trace, 0xFF, (size_t)n * trace_cap) != hipSuccess) return MI_BA_ERR_HIP;
-  }
+  PoseTraceBuf trace;
+  st = trace.setup(n);
+  if (st != MI_BA_OK) return st;
+  a.trace = trace.dev;
+  a.trace_cap = trace.cap;
   const size_t bytes = (size_t)kPoseWaves * 4 * a.lds_obs * 8;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&relative_pose_kernel),
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
@@ -559,25 +538,11 @@ extern "C" mi_ba_status mi_ba_refine_relative_pose_batch(const mi_ba_relative_po
   if (hipGetLastError() != hipSuccess) return MI_BA_ERR_HIP;
   if (hipStreamSynchronize(0) != hipSuccess) return MI_BA_ERR_HIP;
   std::vector<double> out(kOutStride * (size_t)n);
-  if (hipMemcpy(pose.data(), dpose, pose.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(out.data(), dout, out.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
-    return MI_BA_ERR_HIP;
-  if (trace && hipMemcpy(trace, a.trace, (size_t)n * trace_cap, hipMemcpyDeviceToHost) != hipSuccess)
+  if (!pose_download(&pose, dpose) || !pose_download(&out, dout) || trace.download() != MI_BA_OK)
     return MI_BA_ERR_HIP;
   for (const RProblemDev& pb : list) {
     const int k = pb.index;
-    const double* r = &out[kOutStride * (size_t)k];
-    mi_ba_summary& s = summaries[k];
-    s.initial_cost = r[0];
-    s.final_cost = r[1];
-    s.num_successful_steps = (int32_t)r[2];
-    s.num_unsuccessful_steps = (int32_t)r[3];
-    s.termination_type = (int32_t)r[4];
-    s.num_jacobian_evaluations = 1 + s.num_successful_steps;
-    s.num_linear_solver_iterations = s.num_successful_steps + s.num_unsuccessful_steps;
-    // Ceres leaves the user's parameter blocks untouched on FAILURE
-    const bool ok = s.termination_type == MI_BA_CONVERGENCE || s.termination_type == MI_BA_NO_CONVERGENCE ||
-                    s.termination_type == MI_BA_USER_SUCCESS;
+    const bool ok = pose_summary_fill(&out[kOutStride * (size_t)k], &summaries[k]);
     if (ok) {
       for (int m = 0; m < 4; ++m) b->qvec[4 * (size_t)k + m] = pose[8 * (size_t)k + m];
       for (int m = 0; m < 3; ++m) b->tvec[3 * (size_t)k + m] = pose[8 * (size_t)k + 4 + m];
@@ -597,7 +562,7 @@ extern "C" mi_ba_status mi_ba_relative_pose_evaluate(const mi_ba_relative_pose_o
   const int64_t raw0 = b->obs_offsets[0], N = b->obs_offsets[n] - raw0;
   if (N == 0) return MI_BA_OK;
   if (!residuals || !jacobians) return MI_BA_ERR_INVALID_ARGUMENT;
-  st = relative_pose_device(o->device);
+  st = pose_select_device(o->device);
   if (st != MI_BA_OK) return st;
   std::vector<RProblemDev> list;
   std::vector<double> pose(8 * (size_t)n, 0.0);
