@@ -35,7 +35,11 @@
  *   mi_ba_refine_relative_pose_batch
  *                              <- RefineRelativePose (src/estimators/pose.cc:324-352), many
  *                                 image pairs per call
- *   mi_ba_semantic (struct)    <- SemanticBundleAdjustmentOptions depth/semantic maps
+ *   mi_ba_estimate_triangulation_batch / mi_ba_triangulate_points
+ *                              <- EstimateTriangulation (src/estimators/triangulation.cc:132-160),
+ *                                 many tracks per call; TriangulatePoints and
+ *                                 CalculateTriangulationAngles (src/base/triangulation.cc)
+ *   mi_ba_semantic (struct)   <- SemanticBundleAdjustmentOptions depth/semantic maps
  *                                 (src/optim/semantic_bundle_adjustment.h:53-140,
  *                                 semantic_bundle_adjustment.cc:699-906,1021-1068)
  *
@@ -1013,6 +1017,111 @@ int32_t mi_ba_relative_pose_lds_capacity(void);
 mi_ba_status mi_ba_relative_pose_evaluate(const mi_ba_relative_pose_options* options,
                                           const mi_ba_relative_pose_batch* batch, double* residuals,
                                           double* jacobians);
+
+/* --- batched robust triangulation -------------------------------------------
+ * Additive entry points (MI_BA_ABI_VERSION stays 4).
+ * EstimateTriangulation (src/estimators/triangulation.cc:132-160, called per
+ * track from IncrementalTriangulator::Create and CompleteImage): a
+ * LORANSAC<TriangulationEstimator, TriangulationEstimator,
+ * InlierSupportMeasurer, CombinationSampler>.  The sampler draws the pairs
+ * (0,1), (0,2), ..., (n-2,n-1) in order and uses no random number, so the
+ * estimator is deterministic and is matched decision for decision: the trial
+ * order, the support comparison, the local optimisation (at most 10
+ * recursions on the inlier set, each accepted only if it compares better,
+ * ended when the inlier count did not grow), ComputeNumTrials with its three
+ * early returns, the abort test made only for a trial that produced a model,
+ * the one more counted trial after an abort, and both caps of max_num_trials
+ * (the constructor's by min_inlier_ratio, then C(n, 2)).
+ *
+ * The defaults are those of RANSACOptions (optim/ransac.h:47-66) and
+ * EstimateTriangulationOptions (estimators/triangulation.h:123-138);
+ * max_error has none (0, which Check() refuses).  max_num_trials: size_t's
+ * maximum is INT64_MAX here. */
+enum { MI_BA_TRIANGULATION_ANGULAR_ERROR = 0, MI_BA_TRIANGULATION_REPROJECTION_ERROR = 1 };
+
+typedef struct mi_ba_triangulation_options {
+  double min_tri_angle;              /* radians, default 0 */
+  int32_t residual_type;             /* default MI_BA_TRIANGULATION_ANGULAR_ERROR */
+  double max_error;                  /* radians or pixels; the residual is its square; no default */
+  double min_inlier_ratio;           /* default 0.1 */
+  double confidence;                 /* default 0.99 */
+  double dyn_num_trials_multiplier;  /* default 3.0 */
+  int64_t min_num_trials;            /* default 0 */
+  int64_t max_num_trials;            /* default INT64_MAX */
+  int32_t device;                    /* HIP device ordinal, default 0 */
+} mi_ba_triangulation_options;
+
+/* Zeroes the struct (padding included), then sets the defaults above. */
+void mi_ba_default_triangulation_options(mi_ba_triangulation_options* options);
+
+/* A batch of tracks as a struct of arrays.  Track k owns the observations
+ * obs_offsets[k] .. obs_offsets[k + 1), at least two.  An observation names
+ * its view; a view carries PoseData (projection matrix, projection centre,
+ * camera); a camera carries its model and the parameters
+ * camera_param_offsets[c] .. camera_param_offsets[c + 1)
+ * (mi_ba_num_params(camera_model_ids[c]) of them), the layout of the pose
+ * entry points.  points may be NULL with the angular residual when
+ * points_normalized is given.  points_normalized may be NULL: it is then
+ * derived on the device, Camera::ImageToWorld of points under the view's
+ * camera, as the triangulator's callers do on the host
+ * (incremental_triangulator.cc:190-192); that is a build addition.
+ * min_num_trials, when not NULL, replaces the option per track (the
+ * triangulator sets C(n, 2) for n <= 15). */
+typedef struct mi_ba_triangulation_batch {
+  int32_t num_problems;
+  const int64_t* obs_offsets;          /* [num_problems + 1] */
+  const int32_t* view_index;           /* [obs_offsets[n]] */
+  const double* points;                /* nullable [obs_offsets[n]][2] pixels */
+  const double* points_normalized;     /* nullable [obs_offsets[n]][2] */
+  int32_t num_views;
+  const double* proj_matrices;         /* [num_views][12] row-major 3 x 4 */
+  const double* proj_centers;          /* [num_views][3] */
+  const int32_t* camera_index;         /* [num_views] */
+  int32_t num_cameras;
+  const int32_t* camera_model_ids;     /* [num_cameras] MI_BA_* model id */
+  const int64_t* camera_param_offsets; /* [num_cameras + 1] */
+  const double* camera_params;
+  const int64_t* min_num_trials;       /* nullable [num_problems] */
+} mi_ba_triangulation_batch;
+
+/* Estimates every track of the batch in one launch (one wavefront per track,
+ * the whole LO-RANSAC on the device; 64 trials of a round are evaluated
+ * together and committed in trial order).  Per track k: success[k] (the
+ * reference's return value), num_trials[k], num_inliers[k] (the best
+ * support's) and best_is_local[k]; on success xyz[k] and the track's part of
+ * inlier_mask (indexed like the observations; 1 = residual <= max_error^2
+ * under the best model).  A failed track leaves its xyz and mask entries
+ * untouched.  Outputs other than success are nullable.
+ * MI_BA_ERR_INVALID_ARGUMENT, before any device is touched, for what
+ * RANSACOptions::Check and EstimateTriangulationOptions::Check refuse
+ * (max_error <= 0, min_inlier_ratio or confidence outside [0, 1],
+ * min_num_trials > max_num_trials, min_tri_angle < 0; a per-track
+ * min_num_trials likewise), an unknown residual type, a negative count,
+ * offsets that decrease, a track with fewer than two observations, a view or
+ * camera index out of range, a camera model outside the nine supported or
+ * whose parameter count does not fit, the reprojection residual without
+ * points, and neither points nor points_normalized.  Every sum runs in a
+ * fixed order without atomics: a track gives the same bits on every run, at
+ * every position of a batch and alone. */
+mi_ba_status mi_ba_estimate_triangulation_batch(const mi_ba_triangulation_options* options,
+                                                const mi_ba_triangulation_batch* batch, double* xyz,
+                                                uint8_t* inlier_mask, int32_t* success, int64_t* num_trials,
+                                                int32_t* num_inliers, int32_t* best_is_local);
+
+/* Most observations of one track that the kernel keeps resident in LDS; a
+ * longer track streams its records from device memory.  Host only. */
+int32_t mi_ba_triangulation_lds_capacity(void);
+
+/* TriangulatePoints and CalculateTriangulationAngles
+ * (src/base/triangulation.cc:55-70, 147-181), one lane per pair.  With
+ * proj_matrix1 / proj_matrix2 (row-major 3 x 4) and points1 / points2
+ * ([m][2], normalised) the m points are triangulated into xyz ([m][3]);
+ * without them xyz is an input.  With proj_center1 / proj_center2 and angles
+ * ([m]) the triangulation angle of every point is written.  At least one of
+ * the two pairs must be given. */
+mi_ba_status mi_ba_triangulate_points(const double* proj_matrix1, const double* proj_matrix2, int64_t m,
+                                      const double* points1, const double* points2, const double* proj_center1,
+                                      const double* proj_center2, int32_t device, double* xyz, double* angles);
 
 /* Per-kernel HIP-event timing on the context's stream (enabled with
  * mi_ba_set_timing).  name: "reproj_jacobian", "semantic_jacobian", ... */

@@ -330,6 +330,40 @@ class RelativePoseBatch(C.Structure):
     ]
 
 
+class TriangulationOptions(C.Structure):
+    """mi_ba_triangulation_options (EstimateTriangulationOptions with its RANSACOptions)."""
+    _fields_ = [
+        ("min_tri_angle", C.c_double),
+        ("residual_type", C.c_int32),
+        ("max_error", C.c_double),
+        ("min_inlier_ratio", C.c_double),
+        ("confidence", C.c_double),
+        ("dyn_num_trials_multiplier", C.c_double),
+        ("min_num_trials", C.c_int64),
+        ("max_num_trials", C.c_int64),
+        ("device", C.c_int32),
+    ]
+
+
+class TriangulationBatch(C.Structure):
+    _fields_ = [
+        ("num_problems", C.c_int32),
+        ("obs_offsets", _i64p),
+        ("view_index", _i32p),
+        ("points", _dp),
+        ("points_normalized", _dp),
+        ("num_views", C.c_int32),
+        ("proj_matrices", _dp),
+        ("proj_centers", _dp),
+        ("camera_index", _i32p),
+        ("num_cameras", C.c_int32),
+        ("camera_model_ids", _i32p),
+        ("camera_param_offsets", _i64p),
+        ("camera_params", _dp),
+        ("min_num_trials", _i64p),
+    ]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [
         ("camera_model", C.c_int32),
@@ -448,6 +482,13 @@ def load(path: str = LIB_PATH):
     lib.mi_ba_relative_pose_evaluate.argtypes = [C.POINTER(RelativePoseOptions), C.POINTER(RelativePoseBatch), _dp, _dp]
     lib.mi_ba_relative_pose_lds_capacity.argtypes = []
     lib.mi_ba_relative_pose_lds_capacity.restype = C.c_int32
+    lib.mi_ba_default_triangulation_options.argtypes = [C.POINTER(TriangulationOptions)]
+    lib.mi_ba_default_triangulation_options.restype = None
+    lib.mi_ba_estimate_triangulation_batch.argtypes = [C.POINTER(TriangulationOptions), C.POINTER(TriangulationBatch),
+                                                       _dp, _u8p, _i32p, _i64p, _i32p, _i32p]
+    lib.mi_ba_triangulation_lds_capacity.argtypes = []
+    lib.mi_ba_triangulation_lds_capacity.restype = C.c_int32
+    lib.mi_ba_triangulate_points.argtypes = [_dp, _dp, C.c_int64, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp]
     _lib = lib
     return lib
 
@@ -1354,6 +1395,156 @@ def relative_pose_evaluate(options: RelativePoseOptions, problems):
     check(load().mi_ba_relative_pose_evaluate(C.byref(options), C.byref(a.batch), _ptr(r, _dp), _ptr(J, _dp)),
           "mi_ba_relative_pose_evaluate")
     return [(r[a.obs_off[k]:a.obs_off[k + 1]].copy(), J[a.obs_off[k]:a.obs_off[k + 1]].copy()) for k in range(a.n)]
+
+
+TRIANGULATION_ANGULAR_ERROR, TRIANGULATION_REPROJECTION_ERROR = 0, 1
+
+
+def default_triangulation_options(**kw) -> TriangulationOptions:
+    o = TriangulationOptions()
+    load().mi_ba_default_triangulation_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def triangulation_lds_capacity() -> int:
+    return int(load().mi_ba_triangulation_lds_capacity())
+
+
+@dataclass
+class TriangulationViews:
+    """PoseData shared by the tracks of a batch: per view the projection matrix,
+    the projection centre and its camera; per camera the model and parameters."""
+    proj_matrices: np.ndarray            # [V][3][4]
+    proj_centers: np.ndarray             # [V][3]
+    camera_index: np.ndarray             # [V]
+    camera_models: np.ndarray            # [C] model ids
+    camera_params: list                  # [C] parameter arrays
+
+
+@dataclass
+class TriangulationProblem:
+    """One EstimateTriangulation call (estimators/triangulation.h:143): the
+    track's observations, each in a view of the batch's TriangulationViews."""
+    view_index: np.ndarray                          # [n]
+    points: Optional[np.ndarray] = None             # [n][2] pixels
+    points_normalized: Optional[np.ndarray] = None  # [n][2]; None: derived from points on the device
+    min_num_trials: Optional[int] = None            # None: the option's
+
+
+@dataclass
+class TriangulationBatchResult:
+    success: np.ndarray                  # [n] 0 / 1
+    xyz: np.ndarray                      # [n][3]; NaN for a failed track
+    inlier_mask: list                    # [n] bool arrays; all False for a failed track
+    num_trials: np.ndarray               # [n]
+    num_inliers: np.ndarray              # [n]
+    best_is_local: np.ndarray            # [n]
+
+
+class _TriangulationArrays:
+    """The struct of arrays of a list of TriangulationProblem (kept alive
+    beside the ctypes struct that points into it)."""
+
+    def __init__(self, views: TriangulationViews, problems):
+        n = self.n = len(problems)
+        counts = [len(np.asarray(p.view_index).reshape(-1)) for p in problems]
+        self.obs_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        self.view = (np.ascontiguousarray(np.concatenate([np.asarray(p.view_index, np.int32).reshape(-1)
+                                                          for p in problems])) if n else np.zeros(0, np.int32))
+
+        def cat(name):
+            given = [getattr(p, name) is not None for p in problems]
+            if not any(given):
+                return None
+            if not all(given):
+                raise ValueError(f"{name} must be given for every problem of a batch or for none")
+            parts = [np.asarray(getattr(p, name), np.float64).reshape(-1, 2) for p in problems]
+            for a, c in zip(parts, counts):
+                if len(a) != c:
+                    raise ValueError(f"{name} and view_index differ in length")
+            return np.ascontiguousarray(np.concatenate(parts))
+        self.points, self.normalized = cat("points"), cat("points_normalized")
+        self.proj = np.ascontiguousarray(np.asarray(views.proj_matrices, np.float64).reshape(-1, 12))
+        self.centers = np.ascontiguousarray(np.asarray(views.proj_centers, np.float64).reshape(-1, 3))
+        self.view_cam = np.ascontiguousarray(np.asarray(views.camera_index, np.int32).reshape(-1))
+        if not (len(self.proj) == len(self.centers) == len(self.view_cam)):
+            raise ValueError("proj_matrices, proj_centers and camera_index differ in length")
+        self.models = np.ascontiguousarray(np.asarray(views.camera_models, np.int32).reshape(-1))
+        prm = [np.asarray(c, np.float64).reshape(-1) for c in views.camera_params]
+        if len(prm) != len(self.models):
+            raise ValueError("camera_models and camera_params differ in length")
+        self.prm_off = np.concatenate([[0], np.cumsum([len(c) for c in prm])]).astype(np.int64)
+        self.prm = np.ascontiguousarray(np.concatenate(prm)) if prm else np.zeros(0)
+        self.min_trials = None
+        if any(p.min_num_trials is not None for p in problems):
+            self.min_trials = np.array([-1 if p.min_num_trials is None else int(p.min_num_trials) for p in problems],
+                                       np.int64)
+        b = self.batch = TriangulationBatch()
+        b.num_problems = n
+        b.obs_offsets = _ptr(self.obs_off, _i64p)
+        b.view_index = _ptr(self.view, _i32p)
+        b.points = _ptr(self.points, _dp)
+        b.points_normalized = _ptr(self.normalized, _dp)
+        b.num_views = len(self.proj)
+        b.proj_matrices = _ptr(self.proj, _dp)
+        b.proj_centers = _ptr(self.centers, _dp)
+        b.camera_index = _ptr(self.view_cam, _i32p)
+        b.num_cameras = len(self.models)
+        b.camera_model_ids = _ptr(self.models, _i32p)
+        b.camera_param_offsets = _ptr(self.prm_off, _i64p)
+        b.camera_params = _ptr(self.prm, _dp)
+        b.min_num_trials = _ptr(self.min_trials, _i64p)
+
+    def resolve_min_trials(self, options):
+        """A problem without its own min_num_trials takes the option's."""
+        if self.min_trials is not None:
+            self.min_trials[self.min_trials < 0] = int(options.min_num_trials)
+
+
+def estimate_triangulation_batch(options: TriangulationOptions, views: TriangulationViews,
+                                 problems) -> TriangulationBatchResult:
+    """mi_ba_estimate_triangulation_batch: EstimateTriangulation of every
+    track of the list in one launch."""
+    a = _TriangulationArrays(views, problems)
+    a.resolve_min_trials(options)
+    n, total = a.n, int(a.obs_off[-1])
+    xyz = np.full((n, 3), np.nan)
+    mask = np.zeros(max(total, 1), np.uint8)
+    success, inl, local = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    trials = np.zeros(n, np.int64)
+    check(load().mi_ba_estimate_triangulation_batch(C.byref(options), C.byref(a.batch), _ptr(xyz, _dp),
+                                                    _ptr(mask, _u8p), _ptr(success, _i32p), _ptr(trials, _i64p),
+                                                    _ptr(inl, _i32p), _ptr(local, _i32p)),
+          "mi_ba_estimate_triangulation_batch")
+    masks = [mask[a.obs_off[k]:a.obs_off[k + 1]].astype(bool) for k in range(n)]
+    return TriangulationBatchResult(success, xyz, masks, trials, inl, local)
+
+
+def triangulate_points(proj_matrix1=None, proj_matrix2=None, points1=None, points2=None, proj_center1=None,
+                       proj_center2=None, xyz=None, device: int = 0):
+    """mi_ba_triangulate_points: TriangulatePoints of the pairs under the two
+    projection matrices (or the given xyz), and with the two centres
+    CalculateTriangulationAngles.  Returns (xyz [m][3], angles [m] or None)."""
+    tri = proj_matrix1 is not None
+    f = lambda a, shape: None if a is None else np.ascontiguousarray(np.asarray(a, np.float64).reshape(shape))
+    P1, P2, c1, c2 = f(proj_matrix1, 12), f(proj_matrix2, 12), f(proj_center1, 3), f(proj_center2, 3)
+    p1, p2 = f(points1, (-1, 2)), f(points2, (-1, 2))
+    if tri:
+        if p1 is None or p2 is None or len(p1) != len(p2):
+            raise ValueError("points1 and points2 differ in length")
+        out = np.zeros((len(p1), 3))
+    else:
+        out = np.array(np.asarray(xyz, np.float64).reshape(-1, 3))
+    m = len(out)
+    angles = np.zeros(m) if c1 is not None else None
+    check(load().mi_ba_triangulate_points(_ptr(P1, _dp), _ptr(P2, _dp), m, _ptr(p1, _dp), _ptr(p2, _dp),
+                                          _ptr(c1, _dp), _ptr(c2, _dp), device, _ptr(out, _dp), _ptr(angles, _dp)),
+          "mi_ba_triangulate_points")
+    return out, angles
 
 
 def pose_problem_scene(problem: PoseProblem) -> Scene:
