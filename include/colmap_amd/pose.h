@@ -56,6 +56,88 @@ struct AbsolutePoseRefinementOptions {
   }
 };
 
+namespace internal {
+
+// Row k of a batch array of W doubles per row, from and to a std::array.
+template <size_t W>
+inline void PackRow(const std::array<double, W>& v, size_t k, std::vector<double>* rows) {
+  for (size_t m = 0; m < W; ++m) (*rows)[W * k + m] = v[m];
+}
+template <size_t W>
+inline void UnpackRow(const std::vector<double>& rows, size_t k, std::array<double, W>* v) {
+  for (size_t m = 0; m < W; ++m) (*v)[m] = rows[W * k + m];
+}
+
+// The correspondences of one problem into the batch rows from `first` on.
+template <size_t W>
+inline void PackRows(const std::vector<std::array<double, W>>& v, size_t first, std::vector<double>* rows) {
+  for (size_t i = 0; i < v.size(); ++i) PackRow(v[i], first + i, rows);
+}
+inline void PackMask(const std::vector<char>& inlier_mask, size_t first, std::vector<uint8_t>* mask) {
+  for (size_t i = 0; i < inlier_mask.size(); ++i) (*mask)[first + i] = inlier_mask[i] ? 1 : 0;
+}
+
+inline mi_ba_pose_refine_options ToPoseRefineOptions(const AbsolutePoseRefinementOptions& options) {
+  mi_ba_pose_refine_options o;
+  mi_ba_default_pose_refine_options(&o);
+  o.gradient_tolerance = options.gradient_tolerance;
+  o.max_num_iterations = options.max_num_iterations;
+  o.loss_function_scale = options.loss_function_scale;
+  o.refine_focal_length = options.refine_focal_length ? 1 : 0;
+  o.refine_extra_params = options.refine_extra_params ? 1 : 0;
+  o.device = options.device;
+  return o;
+}
+
+// The status of one problem and of the whole call.  Not ThrowStatus: here
+// everything but an invalid argument is a std::runtime_error.
+inline void CheckProblemStatus(int32_t st, const char* what) {
+  if (st != MI_BA_OK) throw std::runtime_error(std::string(what) + ": " + mi_ba_status_string(st));
+}
+inline void CheckCallStatus(mi_ba_status st, const char* what) {
+  if (st == MI_BA_ERR_INVALID_ARGUMENT) throw std::invalid_argument(std::string(what) + ": invalid argument");
+  CheckProblemStatus(st, what);
+}
+
+// What the library returns per problem, and the epilogue every estimator runs
+// for a solved one: its summary and usable flag, and the pose back (the
+// library writes parameters back only where Ceres would).
+struct RefineOutputs {
+  explicit RefineOutputs(int n) : statuses(n), ok(n), sums(n), usable(n, false) {}
+  std::vector<int32_t> statuses, ok;
+  std::vector<mi_ba_summary> sums;
+  std::vector<bool> usable;
+
+  // refine: one of the three mi_ba_refine_*_batch entry points.
+  template <typename Refine, typename Options, typename Batch>
+  void Call(Refine refine, const Options& o, const Batch& b, const char* what) {
+    CheckCallStatus(refine(&o, &b, statuses.data(), sums.data(), ok.data()), what);
+  }
+
+  SolverSummary Finish(size_t k, const std::vector<double>& q, const std::vector<double>& t,
+                       std::array<double, 4>* qvec, std::array<double, 3>* tvec,
+                       std::vector<SolverSummary>* summaries) {
+    const SolverSummary s = ToSummary(sums[k]);
+    if (summaries) (*summaries)[k] = s;
+    UnpackRow(q, k, qvec);
+    UnpackRow(t, k, tvec);
+    usable[k] = ok[k] != 0;
+    return s;
+  }
+};
+
+// The rest of the epilogue of the two absolute estimators.
+inline void FinishAbsolute(const AbsolutePoseRefinementOptions& options, const SolverSummary& s, bool usable,
+                           const std::vector<double>& cov, size_t k, std::array<double, 36>* rot_tvec_covariance) {
+  if (rot_tvec_covariance && usable) UnpackRow(cov, k, rot_tvec_covariance);
+  if (options.print_summary) {
+    PrintHeading2("Pose refinement report");
+    PrintSolverSummary(s);
+  }
+}
+
+}  // namespace internal
+
 // One problem of RefineAbsolutePoses: the arguments of RefineAbsolutePose.
 // rot_tvec_covariance (nullable): row-major 6 x 6, rotation tangent first,
 // then translation.
@@ -91,34 +173,22 @@ inline std::vector<bool> RefineAbsolutePoses(const AbsolutePoseRefinementOptions
     any_cov = any_cov || p.rot_tvec_covariance;
   }
   if (summaries) summaries->assign(n, SolverSummary());
-  std::vector<bool> usable(n, false);
-  if (n == 0) return usable;
+  if (n == 0) return {};
   std::vector<double> p2(2 * (size_t)obs_off[n]), p3(3 * (size_t)obs_off[n]), cams((size_t)cam_off[n]), q(4 * (size_t)n),
       t(3 * (size_t)n), cov(any_cov ? 36 * (size_t)n : 0);
   std::vector<uint8_t> mask((size_t)obs_off[n]);
   std::vector<int32_t> models(n);
   for (int k = 0; k < n; ++k) {
     const AbsolutePoseProblem& p = problems[k];
-    for (size_t i = 0; i < p.points2D->size(); ++i) {
-      const size_t o = (size_t)obs_off[k] + i;
-      p2[2 * o] = (*p.points2D)[i][0];
-      p2[2 * o + 1] = (*p.points2D)[i][1];
-      for (int m = 0; m < 3; ++m) p3[3 * o + m] = (*p.points3D)[i][m];
-      mask[o] = (*p.inlier_mask)[i] ? 1 : 0;
-    }
+    internal::PackRows(*p.points2D, (size_t)obs_off[k], &p2);
+    internal::PackRows(*p.points3D, (size_t)obs_off[k], &p3);
+    internal::PackMask(*p.inlier_mask, (size_t)obs_off[k], &mask);
     models[k] = p.camera->model_id;
     for (size_t m = 0; m < p.camera->params.size(); ++m) cams[(size_t)cam_off[k] + m] = p.camera->params[m];
-    for (int m = 0; m < 4; ++m) q[4 * (size_t)k + m] = (*p.qvec)[m];
-    for (int m = 0; m < 3; ++m) t[3 * (size_t)k + m] = (*p.tvec)[m];
+    internal::PackRow(*p.qvec, k, &q);
+    internal::PackRow(*p.tvec, k, &t);
   }
-  mi_ba_pose_refine_options o;
-  mi_ba_default_pose_refine_options(&o);
-  o.gradient_tolerance = options.gradient_tolerance;
-  o.max_num_iterations = options.max_num_iterations;
-  o.loss_function_scale = options.loss_function_scale;
-  o.refine_focal_length = options.refine_focal_length ? 1 : 0;
-  o.refine_extra_params = options.refine_extra_params ? 1 : 0;
-  o.device = options.device;
+  const mi_ba_pose_refine_options o = internal::ToPoseRefineOptions(options);
   mi_ba_pose_batch b{};
   b.num_problems = n;
   b.obs_offsets = obs_off.data();
@@ -131,40 +201,18 @@ inline std::vector<bool> RefineAbsolutePoses(const AbsolutePoseRefinementOptions
   b.qvec = q.data();
   b.tvec = t.data();
   b.rot_tvec_covariance = any_cov ? cov.data() : nullptr;
-  std::vector<int32_t> statuses(n), ok(n);
-  std::vector<mi_ba_summary> sums(n);
-  const mi_ba_status st = mi_ba_refine_absolute_pose_batch(&o, &b, statuses.data(), sums.data(), ok.data());
-  if (st == MI_BA_ERR_INVALID_ARGUMENT) throw std::invalid_argument("RefineAbsolutePose: invalid argument");
-  if (st != MI_BA_OK) throw std::runtime_error(std::string("RefineAbsolutePose: ") + mi_ba_status_string(st));
+  internal::RefineOutputs out(n);
+  out.Call(mi_ba_refine_absolute_pose_batch, o, b, "RefineAbsolutePose");
   for (int k = 0; k < n; ++k) {
     const AbsolutePoseProblem& p = problems[k];
     // camera_models.h:140-141 throws for an unknown model
-    if (statuses[k] == MI_BA_ERR_UNSUPPORTED) throw std::domain_error("Camera model does not exist");
-    if (statuses[k] != MI_BA_OK) throw std::runtime_error(std::string("RefineAbsolutePose: ") + mi_ba_status_string(statuses[k]));
-    SolverSummary s;
-    s.num_residuals_reduced = sums[k].num_residuals_reduced;
-    s.num_effective_parameters_reduced = sums[k].num_effective_parameters_reduced;
-    s.num_successful_steps = sums[k].num_successful_steps;
-    s.num_unsuccessful_steps = sums[k].num_unsuccessful_steps;
-    s.termination_type = (SolverSummary::TerminationType)sums[k].termination_type;
-    s.initial_cost = sums[k].initial_cost;
-    s.final_cost = sums[k].final_cost;
-    s.num_jacobian_evaluations = sums[k].num_jacobian_evaluations;
-    s.num_linear_solver_iterations = sums[k].num_linear_solver_iterations;
-    if (summaries) (*summaries)[k] = s;
-    // the library writes parameters back only where Ceres would
-    for (int m = 0; m < 4; ++m) (*p.qvec)[m] = q[4 * (size_t)k + m];
-    for (int m = 0; m < 3; ++m) (*p.tvec)[m] = t[3 * (size_t)k + m];
+    if (out.statuses[k] == MI_BA_ERR_UNSUPPORTED) throw std::domain_error("Camera model does not exist");
+    internal::CheckProblemStatus(out.statuses[k], "RefineAbsolutePose");
+    const SolverSummary s = out.Finish(k, q, t, p.qvec, p.tvec, summaries);
     for (size_t m = 0; m < p.camera->params.size(); ++m) p.camera->params[m] = cams[(size_t)cam_off[k] + m];
-    if (p.rot_tvec_covariance && ok[k])
-      for (int m = 0; m < 36; ++m) (*p.rot_tvec_covariance)[m] = cov[36 * (size_t)k + m];
-    usable[k] = ok[k] != 0;
-    if (options.print_summary) {
-      PrintHeading2("Pose refinement report");
-      PrintSolverSummary(s);
-    }
+    internal::FinishAbsolute(options, s, out.usable[k], cov, k, p.rot_tvec_covariance);
   }
-  return usable;
+  return out.usable;
 }
 
 // RefineAbsolutePose (pose.cc:198-322), the reference's argument order.
@@ -235,8 +283,7 @@ inline std::vector<bool> RefineGeneralizedAbsolutePoses(const AbsolutePoseRefine
   }
   options.Check();
   if (summaries) summaries->assign(n, SolverSummary());
-  std::vector<bool> usable(n, false);
-  if (n == 0) return usable;
+  if (n == 0) return {};
   const size_t N = (size_t)obs_off[n], NC = (size_t)cam_off[n];
   std::vector<double> p2(2 * N), p3(3 * N), cams((size_t)prm_off.back()), rq(4 * NC), rt(3 * NC), q(4 * (size_t)n),
       t(3 * (size_t)n), cov(any_cov ? 36 * (size_t)n : 0);
@@ -244,33 +291,22 @@ inline std::vector<bool> RefineGeneralizedAbsolutePoses(const AbsolutePoseRefine
   std::vector<int32_t> cidx(N), models(NC);
   for (int k = 0; k < n; ++k) {
     const GeneralizedAbsolutePoseProblem& p = problems[k];
-    for (size_t i = 0; i < p.points2D->size(); ++i) {
-      const size_t o = (size_t)obs_off[k] + i;
-      p2[2 * o] = (*p.points2D)[i][0];
-      p2[2 * o + 1] = (*p.points2D)[i][1];
-      for (int m = 0; m < 3; ++m) p3[3 * o + m] = (*p.points3D)[i][m];
-      mask[o] = (*p.inlier_mask)[i] ? 1 : 0;
-      cidx[o] = (int32_t)(*p.camera_idxs)[i];
-    }
+    internal::PackRows(*p.points2D, (size_t)obs_off[k], &p2);
+    internal::PackRows(*p.points3D, (size_t)obs_off[k], &p3);
+    internal::PackMask(*p.inlier_mask, (size_t)obs_off[k], &mask);
+    for (size_t i = 0; i < p.camera_idxs->size(); ++i) cidx[(size_t)obs_off[k] + i] = (int32_t)(*p.camera_idxs)[i];
     for (size_t c = 0; c < p.cameras->size(); ++c) {
       const size_t g = (size_t)cam_off[k] + c;
       const Camera& cam = (*p.cameras)[c];
       models[g] = cam.model_id;
       for (size_t m = 0; m < cam.params.size(); ++m) cams[(size_t)prm_off[g] + m] = cam.params[m];
-      for (int m = 0; m < 4; ++m) rq[4 * g + m] = (*p.rig_qvecs)[c][m];
-      for (int m = 0; m < 3; ++m) rt[3 * g + m] = (*p.rig_tvecs)[c][m];
+      internal::PackRow((*p.rig_qvecs)[c], g, &rq);
+      internal::PackRow((*p.rig_tvecs)[c], g, &rt);
     }
-    for (int m = 0; m < 4; ++m) q[4 * (size_t)k + m] = (*p.qvec)[m];
-    for (int m = 0; m < 3; ++m) t[3 * (size_t)k + m] = (*p.tvec)[m];
+    internal::PackRow(*p.qvec, k, &q);
+    internal::PackRow(*p.tvec, k, &t);
   }
-  mi_ba_pose_refine_options o;
-  mi_ba_default_pose_refine_options(&o);
-  o.gradient_tolerance = options.gradient_tolerance;
-  o.max_num_iterations = options.max_num_iterations;
-  o.loss_function_scale = options.loss_function_scale;
-  o.refine_focal_length = options.refine_focal_length ? 1 : 0;
-  o.refine_extra_params = options.refine_extra_params ? 1 : 0;
-  o.device = options.device;
+  const mi_ba_pose_refine_options o = internal::ToPoseRefineOptions(options);
   mi_ba_generalized_pose_batch b{};
   b.num_problems = n;
   b.obs_offsets = obs_off.data();
@@ -287,49 +323,26 @@ inline std::vector<bool> RefineGeneralizedAbsolutePoses(const AbsolutePoseRefine
   b.qvec = q.data();
   b.tvec = t.data();
   b.rot_tvec_covariance = any_cov ? cov.data() : nullptr;
-  std::vector<int32_t> statuses(n), ok(n);
-  std::vector<mi_ba_summary> sums(n);
-  const mi_ba_status st = mi_ba_refine_generalized_absolute_pose_batch(&o, &b, statuses.data(), sums.data(), ok.data());
-  if (st == MI_BA_ERR_INVALID_ARGUMENT) throw std::invalid_argument("RefineGeneralizedAbsolutePose: invalid argument");
-  if (st != MI_BA_OK) throw std::runtime_error(std::string("RefineGeneralizedAbsolutePose: ") + mi_ba_status_string(st));
+  internal::RefineOutputs out(n);
+  out.Call(mi_ba_refine_generalized_absolute_pose_batch, o, b, "RefineGeneralizedAbsolutePose");
   for (int k = 0; k < n; ++k) {
     const GeneralizedAbsolutePoseProblem& p = problems[k];
-    if (statuses[k] == MI_BA_ERR_UNSUPPORTED) {
+    if (out.statuses[k] == MI_BA_ERR_UNSUPPORTED) {
       // camera_models.h:140-141 throws for an unknown model (one with inliers)
       for (size_t i = 0; i < p.camera_idxs->size(); ++i)
         if ((*p.inlier_mask)[i] && mi_ba_num_params((*p.cameras)[(*p.camera_idxs)[i]].model_id) < 0)
           throw std::domain_error("Camera model does not exist");
       throw std::runtime_error("RefineGeneralizedAbsolutePose: the rig exceeds mi_ba_generalized_pose_limits");
     }
-    if (statuses[k] != MI_BA_OK)
-      throw std::runtime_error(std::string("RefineGeneralizedAbsolutePose: ") + mi_ba_status_string(statuses[k]));
-    SolverSummary s;
-    s.num_residuals_reduced = sums[k].num_residuals_reduced;
-    s.num_effective_parameters_reduced = sums[k].num_effective_parameters_reduced;
-    s.num_successful_steps = sums[k].num_successful_steps;
-    s.num_unsuccessful_steps = sums[k].num_unsuccessful_steps;
-    s.termination_type = (SolverSummary::TerminationType)sums[k].termination_type;
-    s.initial_cost = sums[k].initial_cost;
-    s.final_cost = sums[k].final_cost;
-    s.num_jacobian_evaluations = sums[k].num_jacobian_evaluations;
-    s.num_linear_solver_iterations = sums[k].num_linear_solver_iterations;
-    if (summaries) (*summaries)[k] = s;
-    // the library writes parameters back only where Ceres would
-    for (int m = 0; m < 4; ++m) (*p.qvec)[m] = q[4 * (size_t)k + m];
-    for (int m = 0; m < 3; ++m) (*p.tvec)[m] = t[3 * (size_t)k + m];
+    internal::CheckProblemStatus(out.statuses[k], "RefineGeneralizedAbsolutePose");
+    const SolverSummary s = out.Finish(k, q, t, p.qvec, p.tvec, summaries);
     for (size_t c = 0; c < p.cameras->size(); ++c) {
       Camera& cam = (*p.cameras)[c];
       for (size_t m = 0; m < cam.params.size(); ++m) cam.params[m] = cams[(size_t)prm_off[(size_t)cam_off[k] + c] + m];
     }
-    if (p.rot_tvec_covariance && ok[k])
-      for (int m = 0; m < 36; ++m) (*p.rot_tvec_covariance)[m] = cov[36 * (size_t)k + m];
-    usable[k] = ok[k] != 0;
-    if (options.print_summary) {
-      PrintHeading2("Pose refinement report");
-      PrintSolverSummary(s);
-    }
+    internal::FinishAbsolute(options, s, out.usable[k], cov, k, p.rot_tvec_covariance);
   }
-  return usable;
+  return out.usable;
 }
 
 // RefineGeneralizedAbsolutePose (pose.cc:354-520), the reference's argument order.
@@ -415,21 +428,15 @@ inline std::vector<bool> RefineRelativePoses(const RelativePoseRefinementOptions
   }
   options.Check();
   if (summaries) summaries->assign(n, SolverSummary());
-  std::vector<bool> usable(n, false);
-  if (n == 0) return usable;
+  if (n == 0) return {};
   const size_t N = (size_t)obs_off[n];
   std::vector<double> p1(2 * N), p2(2 * N), q(4 * (size_t)n), t(3 * (size_t)n);
   for (int k = 0; k < n; ++k) {
     const RelativePoseProblem& p = problems[k];
-    for (size_t i = 0; i < p.points1->size(); ++i) {
-      const size_t o = (size_t)obs_off[k] + i;
-      p1[2 * o] = (*p.points1)[i][0];
-      p1[2 * o + 1] = (*p.points1)[i][1];
-      p2[2 * o] = (*p.points2)[i][0];
-      p2[2 * o + 1] = (*p.points2)[i][1];
-    }
-    for (int m = 0; m < 4; ++m) q[4 * (size_t)k + m] = (*p.qvec)[m];
-    for (int m = 0; m < 3; ++m) t[3 * (size_t)k + m] = (*p.tvec)[m];
+    internal::PackRows(*p.points1, (size_t)obs_off[k], &p1);
+    internal::PackRows(*p.points2, (size_t)obs_off[k], &p2);
+    internal::PackRow(*p.qvec, k, &q);
+    internal::PackRow(*p.tvec, k, &t);
   }
   mi_ba_relative_pose_options o;
   mi_ba_default_relative_pose_options(&o);
@@ -446,31 +453,14 @@ inline std::vector<bool> RefineRelativePoses(const RelativePoseRefinementOptions
   b.points2 = p2.data();
   b.qvec = q.data();
   b.tvec = t.data();
-  std::vector<int32_t> statuses(n), ok(n);
-  std::vector<mi_ba_summary> sums(n);
-  const mi_ba_status st = mi_ba_refine_relative_pose_batch(&o, &b, statuses.data(), sums.data(), ok.data());
-  if (st == MI_BA_ERR_INVALID_ARGUMENT) throw std::invalid_argument("RefineRelativePose: invalid argument");
-  if (st != MI_BA_OK) throw std::runtime_error(std::string("RefineRelativePose: ") + mi_ba_status_string(st));
+  internal::RefineOutputs out(n);
+  out.Call(mi_ba_refine_relative_pose_batch, o, b, "RefineRelativePose");
   for (int k = 0; k < n; ++k) {
     const RelativePoseProblem& p = problems[k];
-    if (statuses[k] != MI_BA_OK) throw std::runtime_error(std::string("RefineRelativePose: ") + mi_ba_status_string(statuses[k]));
-    SolverSummary s;
-    s.num_residuals_reduced = sums[k].num_residuals_reduced;
-    s.num_effective_parameters_reduced = sums[k].num_effective_parameters_reduced;
-    s.num_successful_steps = sums[k].num_successful_steps;
-    s.num_unsuccessful_steps = sums[k].num_unsuccessful_steps;
-    s.termination_type = (SolverSummary::TerminationType)sums[k].termination_type;
-    s.initial_cost = sums[k].initial_cost;
-    s.final_cost = sums[k].final_cost;
-    s.num_jacobian_evaluations = sums[k].num_jacobian_evaluations;
-    s.num_linear_solver_iterations = sums[k].num_linear_solver_iterations;
-    if (summaries) (*summaries)[k] = s;
-    // the library writes parameters back only where Ceres would
-    for (int m = 0; m < 4; ++m) (*p.qvec)[m] = q[4 * (size_t)k + m];
-    for (int m = 0; m < 3; ++m) (*p.tvec)[m] = t[3 * (size_t)k + m];
-    usable[k] = ok[k] != 0;
+    internal::CheckProblemStatus(out.statuses[k], "RefineRelativePose");
+    out.Finish(k, q, t, p.qvec, p.tvec, summaries);
   }
-  return usable;
+  return out.usable;
 }
 
 // RefineRelativePose (pose.cc:324-352), the reference's argument order.

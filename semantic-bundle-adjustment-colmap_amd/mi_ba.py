@@ -525,14 +525,20 @@ def check(status: int, what: str = ""):
         raise MiBaError(status, what)
 
 
-def default_options(**kw) -> Options:
-    o = Options()
-    load().mi_ba_default_options(C.byref(o))
+def _defaults(struct, fill: str, kw):
+    """A struct with the library's defaults (its C function `fill`) and the
+    keyword overrides on top."""
+    o = struct()
+    getattr(load(), fill)(C.byref(o))
     for k, v in kw.items():
         if not hasattr(o, k):
             raise AttributeError(k)
         setattr(o, k, v)
     return o
+
+
+def default_options(**kw) -> Options:
+    return _defaults(Options, "mi_ba_default_options", kw)
 
 
 @dataclass
@@ -1039,13 +1045,72 @@ def solve_batch(options, scenes, semantics=None, max_concurrent: int = 8):
 
 
 def default_pose_refine_options(**kw) -> PoseRefineOptions:
-    o = PoseRefineOptions()
-    load().mi_ba_default_pose_refine_options(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _defaults(PoseRefineOptions, "mi_ba_default_pose_refine_options", kw)
+
+
+# What the struct-of-arrays classes of the batched estimators (_PoseArrays,
+# _GeneralizedPoseArrays, _RelativePoseArrays, _TriangulationArrays) share.
+
+def _offsets(counts):
+    return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+
+
+def _rows(xs, w, dtype=np.float64):
+    """The row blocks of the list xs under each other: [sum of rows][w]."""
+    if not xs:
+        return np.zeros((0, w), dtype)
+    return np.ascontiguousarray(np.concatenate([np.asarray(x, dtype).reshape(-1, w) for x in xs]))
+
+
+def _inlier_mask(problems, counts):
+    """uint8 [sum of counts], nonzero = inlier, a problem without a mask all
+    ones; None when no problem has one."""
+    if all(p.inlier_mask is None for p in problems):
+        return None
+    return np.ascontiguousarray(np.concatenate(
+        [np.ones(c, np.uint8) if p.inlier_mask is None else (np.asarray(p.inlier_mask) != 0).astype(np.uint8)
+         for p, c in zip(problems, counts)]))
+
+
+def _covariance(covariance, n):
+    """True: zeros [n][6][6]; an array: its copy; False or None: None."""
+    if covariance is True:
+        return np.zeros((n, 6, 6))
+    if covariance is not False and covariance is not None:
+        return np.ascontiguousarray(covariance, dtype=np.float64).reshape(n, 6, 6).copy()
+    return None
+
+
+def _pose_rows(problems):
+    """(qvec [n][4], tvec [n][3]) of the problems."""
+    n = len(problems)
+    return (np.ascontiguousarray(np.array([p.qvec for p in problems], np.float64).reshape(n, 4)),
+            np.ascontiguousarray(np.array([p.tvec for p in problems], np.float64).reshape(n, 3)))
+
+
+def _check_trace(trace, n):
+    if trace is not None:
+        assert trace.dtype == np.uint8 and trace.flags.c_contiguous and trace.shape[0] == n
+
+
+def _refine(entry: str, options, arrays, trace):
+    """One mi_ba_refine_*_batch entry point on arrays.batch, the LM trace
+    (mi_ba_pose_refine_set_trace) armed for the call only.  Returns
+    (statuses, summaries, usable)."""
+    n = arrays.n
+    st = np.zeros(n, np.int32)
+    us = np.zeros(n, np.int32)
+    sums = (Summary * max(n, 1))()
+    if trace is not None:
+        load().mi_ba_pose_refine_set_trace(_ptr(trace, _u8p), int(trace.shape[1]))
+    try:
+        rc = getattr(load(), entry)(C.byref(options), C.byref(arrays.batch), _ptr(st, _i32p),
+                                    C.cast(sums, C.c_void_p), _ptr(us, _i32p))
+    finally:
+        if trace is not None:
+            load().mi_ba_pose_refine_set_trace(None, 0)
+    check(rc, entry)
+    return st, list(sums)[:n], us
 
 
 def pose_refine_intrinsics(model: int, refine_focal_length: bool = True, refine_extra_params: bool = True):
@@ -1089,6 +1154,41 @@ class PoseBatchResult:
     covariance: Optional[np.ndarray]     # [n][6][6] (rotation tangent, translation) or None
 
 
+class _PoseArrays:
+    """The struct of arrays of a list of PoseProblem (kept alive beside the
+    ctypes struct that points into it)."""
+
+    def __init__(self, problems, covariance=False):
+        n = self.n = len(problems)
+        counts = [int(np.asarray(p.points2D).reshape(-1, 2).shape[0]) for p in problems]
+        for p, c in zip(problems, counts):
+            if np.asarray(p.points3D).reshape(-1, 3).shape[0] != c:
+                raise ValueError("points2D and points3D differ in length")
+            if p.inlier_mask is not None and len(p.inlier_mask) != c:
+                raise ValueError("inlier_mask and points2D differ in length")
+        self.obs_off = _offsets(counts)
+        self.p2, self.p3 = _rows([p.points2D for p in problems], 2), _rows([p.points3D for p in problems], 3)
+        self.mask = _inlier_mask(problems, counts)
+        self.models = np.array([p.camera_model for p in problems], np.int32)
+        self.cam_off = _offsets([len(p.camera_params) for p in problems])
+        self.cams = np.ascontiguousarray(np.concatenate([np.asarray(p.camera_params, np.float64) for p in problems])
+                                         if n else np.zeros(0))
+        self.q, self.t = _pose_rows(problems)
+        self.cov = _covariance(covariance, n)
+        b = self.batch = PoseBatch()
+        b.num_problems = n
+        b.obs_offsets = _ptr(self.obs_off, _i64p)
+        b.points2D = _ptr(self.p2, _dp)
+        b.points3D = _ptr(self.p3, _dp)
+        b.inlier_mask = _ptr(self.mask, _u8p)
+        b.camera_model_ids = _ptr(self.models, _i32p)
+        b.camera_param_offsets = _ptr(self.cam_off, _i64p)
+        b.camera_params = _ptr(self.cams, _dp)
+        b.qvec = _ptr(self.q, _dp)
+        b.tvec = _ptr(self.t, _dp)
+        b.rot_tvec_covariance = _ptr(self.cov, _dp)
+
+
 def refine_absolute_pose_batch(options: PoseRefineOptions, problems, covariance=False,
                                trace: Optional[np.ndarray] = None) -> PoseBatchResult:
     """mi_ba_refine_absolute_pose_batch: every problem of the list in one
@@ -1096,60 +1196,11 @@ def refine_absolute_pose_batch(options: PoseRefineOptions, problems, covariance=
     in the result.  covariance: True, or an [n][6][6] array whose rows of
     problems without a covariance are left as given.  trace: a uint8 array
     [n][cap] that receives the LM trace (mi_ba_pose_refine_set_trace)."""
-    n = len(problems)
-    if trace is not None:
-        assert trace.dtype == np.uint8 and trace.flags.c_contiguous and trace.shape[0] == n
-    counts = [int(np.asarray(p.points2D).reshape(-1, 2).shape[0]) for p in problems]
-    for p, c in zip(problems, counts):
-        if np.asarray(p.points3D).reshape(-1, 3).shape[0] != c:
-            raise ValueError("points2D and points3D differ in length")
-        if p.inlier_mask is not None and len(p.inlier_mask) != c:
-            raise ValueError("inlier_mask and points2D differ in length")
-    obs_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-    cat = lambda xs, w: (np.ascontiguousarray(np.concatenate([np.asarray(x, np.float64).reshape(-1, w) for x in xs]))
-                         if n else np.zeros((0, w)))
-    p2, p3 = cat([p.points2D for p in problems], 2), cat([p.points3D for p in problems], 3)
-    mask = None
-    if any(p.inlier_mask is not None for p in problems):
-        mask = np.ascontiguousarray(np.concatenate(
-            [np.ones(c, np.uint8) if p.inlier_mask is None else (np.asarray(p.inlier_mask) != 0).astype(np.uint8)
-             for p, c in zip(problems, counts)]))
-    models = np.array([p.camera_model for p in problems], np.int32)
-    cam_off = np.concatenate([[0], np.cumsum([len(p.camera_params) for p in problems])]).astype(np.int64)
-    cams = np.ascontiguousarray(np.concatenate([np.asarray(p.camera_params, np.float64) for p in problems])
-                                if n else np.zeros(0))
-    q = np.ascontiguousarray(np.array([p.qvec for p in problems], np.float64).reshape(n, 4))
-    t = np.ascontiguousarray(np.array([p.tvec for p in problems], np.float64).reshape(n, 3))
-    cov = None
-    if covariance is True:
-        cov = np.zeros((n, 6, 6))
-    elif covariance is not False and covariance is not None:
-        cov = np.ascontiguousarray(covariance, dtype=np.float64).reshape(n, 6, 6).copy()
-    b = PoseBatch()
-    b.num_problems = n
-    b.obs_offsets = _ptr(obs_off, _i64p)
-    b.points2D = _ptr(p2, _dp)
-    b.points3D = _ptr(p3, _dp)
-    b.inlier_mask = _ptr(mask, _u8p)
-    b.camera_model_ids = _ptr(models, _i32p)
-    b.camera_param_offsets = _ptr(cam_off, _i64p)
-    b.camera_params = _ptr(cams, _dp)
-    b.qvec = _ptr(q, _dp)
-    b.tvec = _ptr(t, _dp)
-    b.rot_tvec_covariance = _ptr(cov, _dp)
-    st = np.zeros(n, np.int32)
-    us = np.zeros(n, np.int32)
-    sums = (Summary * max(n, 1))()
-    if trace is not None:
-        load().mi_ba_pose_refine_set_trace(_ptr(trace, _u8p), int(trace.shape[1]))
-    try:
-        rc = load().mi_ba_refine_absolute_pose_batch(C.byref(options), C.byref(b), _ptr(st, _i32p),
-                                                     C.cast(sums, C.c_void_p), _ptr(us, _i32p))
-    finally:
-        if trace is not None:
-            load().mi_ba_pose_refine_set_trace(None, 0)
-    check(rc, "mi_ba_refine_absolute_pose_batch")
-    return PoseBatchResult(st, list(sums)[:n], us, q, t, [cams[cam_off[k]:cam_off[k + 1]].copy() for k in range(n)], cov)
+    _check_trace(trace, len(problems))
+    a = _PoseArrays(problems, covariance)
+    st, sums, us = _refine("mi_ba_refine_absolute_pose_batch", options, a, trace)
+    return PoseBatchResult(st, sums, us, a.q, a.t, [a.cams[a.cam_off[k]:a.cam_off[k + 1]].copy() for k in range(a.n)],
+                           a.cov)
 
 
 def refine_absolute_pose(options: PoseRefineOptions, problem: PoseProblem, covariance=False) -> PoseBatchResult:
@@ -1200,30 +1251,18 @@ class _GeneralizedPoseArrays:
             if len(p.camera_params) != nc or np.asarray(p.rig_qvecs).reshape(-1, 4).shape[0] != nc or \
                     np.asarray(p.rig_tvecs).reshape(-1, 3).shape[0] != nc:
                 raise ValueError("cameras, rig_qvecs and rig_tvecs differ in length")
-        cat = lambda xs, w, dt=np.float64: (np.ascontiguousarray(
-            np.concatenate([np.asarray(x, dt).reshape(-1, w) for x in xs])) if n else np.zeros((0, w), dt))
-        self.obs_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        self.p2, self.p3 = cat([p.points2D for p in problems], 2), cat([p.points3D for p in problems], 3)
-        self.cidx = cat([p.camera_idxs for p in problems], 1, np.int32).reshape(-1)
-        self.mask = None
-        if any(p.inlier_mask is not None for p in problems):
-            self.mask = np.ascontiguousarray(np.concatenate(
-                [np.ones(c, np.uint8) if p.inlier_mask is None else (np.asarray(p.inlier_mask) != 0).astype(np.uint8)
-                 for p, c in zip(problems, counts)]))
-        self.cam_off = np.concatenate([[0], np.cumsum([len(p.camera_models) for p in problems])]).astype(np.int64)
+        self.obs_off = _offsets(counts)
+        self.p2, self.p3 = _rows([p.points2D for p in problems], 2), _rows([p.points3D for p in problems], 3)
+        self.cidx = _rows([p.camera_idxs for p in problems], 1, np.int32).reshape(-1)
+        self.mask = _inlier_mask(problems, counts)
+        self.cam_off = _offsets([len(p.camera_models) for p in problems])
         self.models = np.array([m for p in problems for m in p.camera_models], np.int32)
-        plens = [len(c) for p in problems for c in p.camera_params]
-        self.prm_off = np.concatenate([[0], np.cumsum(plens)]).astype(np.int64)
+        self.prm_off = _offsets([len(c) for p in problems for c in p.camera_params])
         self.cams = np.ascontiguousarray(np.concatenate(
             [np.zeros(0)] + [np.asarray(c, np.float64).reshape(-1) for p in problems for c in p.camera_params]))
-        self.rq, self.rt = cat([p.rig_qvecs for p in problems], 4), cat([p.rig_tvecs for p in problems], 3)
-        self.q = np.ascontiguousarray(np.array([p.qvec for p in problems], np.float64).reshape(n, 4))
-        self.t = np.ascontiguousarray(np.array([p.tvec for p in problems], np.float64).reshape(n, 3))
-        self.cov = None
-        if covariance is True:
-            self.cov = np.zeros((n, 6, 6))
-        elif covariance is not False and covariance is not None:
-            self.cov = np.ascontiguousarray(covariance, dtype=np.float64).reshape(n, 6, 6).copy()
+        self.rq, self.rt = _rows([p.rig_qvecs for p in problems], 4), _rows([p.rig_tvecs for p in problems], 3)
+        self.q, self.t = _pose_rows(problems)
+        self.cov = _covariance(covariance, n)
         b = self.batch = GeneralizedPoseBatch()
         b.num_problems = n
         b.obs_offsets = _ptr(self.obs_off, _i64p)
@@ -1268,34 +1307,15 @@ def refine_generalized_absolute_pose_batch(options: PoseRefineOptions, problems,
     list in one launch.  As refine_absolute_pose_batch; camera_params of the
     result is, per problem, the list of its cameras' parameter arrays."""
     a = _GeneralizedPoseArrays(problems, covariance)
-    n = a.n
-    if trace is not None:
-        assert trace.dtype == np.uint8 and trace.flags.c_contiguous and trace.shape[0] == n
-    st = np.zeros(n, np.int32)
-    us = np.zeros(n, np.int32)
-    sums = (Summary * max(n, 1))()
-    if trace is not None:
-        load().mi_ba_pose_refine_set_trace(_ptr(trace, _u8p), int(trace.shape[1]))
-    try:
-        rc = load().mi_ba_refine_generalized_absolute_pose_batch(C.byref(options), C.byref(a.batch), _ptr(st, _i32p),
-                                                                 C.cast(sums, C.c_void_p), _ptr(us, _i32p))
-    finally:
-        if trace is not None:
-            load().mi_ba_pose_refine_set_trace(None, 0)
-    check(rc, "mi_ba_refine_generalized_absolute_pose_batch")
+    _check_trace(trace, a.n)
+    st, sums, us = _refine("mi_ba_refine_generalized_absolute_pose_batch", options, a, trace)
     cams = [[a.cams[a.prm_off[c]:a.prm_off[c + 1]].copy() for c in range(a.cam_off[k], a.cam_off[k + 1])]
-            for k in range(n)]
-    return PoseBatchResult(st, list(sums)[:n], us, a.q, a.t, cams, a.cov)
+            for k in range(a.n)]
+    return PoseBatchResult(st, sums, us, a.q, a.t, cams, a.cov)
 
 
 def default_relative_pose_options(**kw) -> RelativePoseOptions:
-    o = RelativePoseOptions()
-    load().mi_ba_default_relative_pose_options(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _defaults(RelativePoseOptions, "mi_ba_default_relative_pose_options", kw)
 
 
 def relative_pose_lds_capacity() -> int:
@@ -1339,17 +1359,10 @@ class _RelativePoseArrays:
                 raise ValueError("points1 and points2 differ in length")
             if p.inlier_mask is not None and len(p.inlier_mask) != c:
                 raise ValueError("inlier_mask and points1 differ in length")
-        cat = lambda xs: (np.ascontiguousarray(np.concatenate([np.asarray(x, np.float64).reshape(-1, 2) for x in xs]))
-                          if n else np.zeros((0, 2)))
-        self.obs_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        self.p1, self.p2 = cat([p.points1 for p in problems]), cat([p.points2 for p in problems])
-        self.mask = None
-        if any(p.inlier_mask is not None for p in problems):
-            self.mask = np.ascontiguousarray(np.concatenate(
-                [np.ones(c, np.uint8) if p.inlier_mask is None else (np.asarray(p.inlier_mask) != 0).astype(np.uint8)
-                 for p, c in zip(problems, counts)]))
-        self.q = np.ascontiguousarray(np.array([p.qvec for p in problems], np.float64).reshape(n, 4))
-        self.t = np.ascontiguousarray(np.array([p.tvec for p in problems], np.float64).reshape(n, 3))
+        self.obs_off = _offsets(counts)
+        self.p1, self.p2 = _rows([p.points1 for p in problems], 2), _rows([p.points2 for p in problems], 2)
+        self.mask = _inlier_mask(problems, counts)
+        self.q, self.t = _pose_rows(problems)
         b = self.batch = RelativePoseBatch()
         b.num_problems = n
         b.obs_offsets = _ptr(self.obs_off, _i64p)
@@ -1367,22 +1380,9 @@ def refine_relative_pose_batch(options: RelativePoseOptions, problems,
     in the result.  trace: a uint8 array [n][cap] that receives the LM trace
     (mi_ba_pose_refine_set_trace)."""
     a = _RelativePoseArrays(problems)
-    n = a.n
-    if trace is not None:
-        assert trace.dtype == np.uint8 and trace.flags.c_contiguous and trace.shape[0] == n
-    st = np.zeros(n, np.int32)
-    us = np.zeros(n, np.int32)
-    sums = (Summary * max(n, 1))()
-    if trace is not None:
-        load().mi_ba_pose_refine_set_trace(_ptr(trace, _u8p), int(trace.shape[1]))
-    try:
-        rc = load().mi_ba_refine_relative_pose_batch(C.byref(options), C.byref(a.batch), _ptr(st, _i32p),
-                                                     C.cast(sums, C.c_void_p), _ptr(us, _i32p))
-    finally:
-        if trace is not None:
-            load().mi_ba_pose_refine_set_trace(None, 0)
-    check(rc, "mi_ba_refine_relative_pose_batch")
-    return RelativePoseBatchResult(st, list(sums)[:n], us, a.q, a.t)
+    _check_trace(trace, a.n)
+    st, sums, us = _refine("mi_ba_refine_relative_pose_batch", options, a, trace)
+    return RelativePoseBatchResult(st, sums, us, a.q, a.t)
 
 
 def relative_pose_evaluate(options: RelativePoseOptions, problems):
@@ -1401,13 +1401,7 @@ TRIANGULATION_ANGULAR_ERROR, TRIANGULATION_REPROJECTION_ERROR = 0, 1
 
 
 def default_triangulation_options(**kw) -> TriangulationOptions:
-    o = TriangulationOptions()
-    load().mi_ba_default_triangulation_options(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _defaults(TriangulationOptions, "mi_ba_default_triangulation_options", kw)
 
 
 def triangulation_lds_capacity() -> int:
@@ -1452,9 +1446,8 @@ class _TriangulationArrays:
     def __init__(self, views: TriangulationViews, problems):
         n = self.n = len(problems)
         counts = [len(np.asarray(p.view_index).reshape(-1)) for p in problems]
-        self.obs_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        self.view = (np.ascontiguousarray(np.concatenate([np.asarray(p.view_index, np.int32).reshape(-1)
-                                                          for p in problems])) if n else np.zeros(0, np.int32))
+        self.obs_off = _offsets(counts)
+        self.view = _rows([p.view_index for p in problems], 1, np.int32).reshape(-1)
 
         def cat(name):
             given = [getattr(p, name) is not None for p in problems]
@@ -1466,7 +1459,7 @@ class _TriangulationArrays:
             for a, c in zip(parts, counts):
                 if len(a) != c:
                     raise ValueError(f"{name} and view_index differ in length")
-            return np.ascontiguousarray(np.concatenate(parts))
+            return _rows(parts, 2)
         self.points, self.normalized = cat("points"), cat("points_normalized")
         self.proj = np.ascontiguousarray(np.asarray(views.proj_matrices, np.float64).reshape(-1, 12))
         self.centers = np.ascontiguousarray(np.asarray(views.proj_centers, np.float64).reshape(-1, 3))
@@ -1477,7 +1470,7 @@ class _TriangulationArrays:
         prm = [np.asarray(c, np.float64).reshape(-1) for c in views.camera_params]
         if len(prm) != len(self.models):
             raise ValueError("camera_models and camera_params differ in length")
-        self.prm_off = np.concatenate([[0], np.cumsum([len(c) for c in prm])]).astype(np.int64)
+        self.prm_off = _offsets([len(c) for c in prm])
         self.prm = np.ascontiguousarray(np.concatenate(prm)) if prm else np.zeros(0)
         self.min_trials = None
         if any(p.min_num_trials is not None for p in problems):

@@ -8,6 +8,7 @@ import numpy as np
 import camera_model_ref as cm
 import generalized_pose_reference as gref
 import mi_ba
+from estimator_testing import qmul, quat, same_stop, ulp_solves
 
 TRUE_PARAMS = {
     mi_ba.SIMPLE_PINHOLE: [1200.0, 500.0, 500.0],
@@ -32,17 +33,6 @@ START_OFFSET = {
     mi_ba.RADIAL_FISHEYE: [10.0, 0.0, 0.0, 5e-3, 5e-3],
 }
 ALL_MODELS = sorted(TRUE_PARAMS)
-
-
-def quat(axis_angle):
-    a = np.linalg.norm(axis_angle)
-    if a == 0:
-        return np.array([1.0, 0, 0, 0])
-    return np.concatenate([[np.cos(a / 2)], np.sin(a / 2) * np.asarray(axis_angle) / a])
-
-
-def qmul(z, w):
-    return np.array([z[0] * w[0] - z[1:] @ w[1:], *(z[0] * w[1:] + w[0] * z[1:] + np.cross(z[1:], w[1:]))])
 
 
 def make_rig_problem(models, counts, seed, identity=False, outlier_fraction=0.1, outlier_px=40.0, noise_px=0.5,
@@ -109,27 +99,12 @@ def reference_solve(pr, rf=True, re=True, **kw):
     return reference_problem(pr, rf, re).solve(**kw)
 
 
-def ulp_perturbed(problem, rng):
-    """The problem with every input coordinate moved by -1, 0 or +1 ulp."""
-    b = problem.copy()
-    for name in ("tvec", "points2D", "points3D"):
-        a = getattr(b, name)
-        s = rng.choice([-1, 0, 1], a.shape).astype(float)
-        a[:] = np.where(s == 0, a, np.nextafter(a, a + s))
-    return b
-
-
 def is_stable(problem, result, rf, re, **kw):
     """pose_cases.is_stable applied to the reference: its step counts and stop
     survive ulp perturbations of the inputs and its final cost moves by less
     than 1e-7 relative under them."""
-    rng = np.random.default_rng(7)
-    for _ in range(3):
-        s = reference_solve(ulp_perturbed(problem, rng), rf, re, **kw)
-        if (s.num_successful_steps, s.num_unsuccessful_steps, s.termination_type) != (
-                result.num_successful_steps, result.num_unsuccessful_steps, result.termination_type):
-            return False
-        if abs(s.final_cost - result.final_cost) > 1e-7 * result.final_cost:
+    for s in ulp_solves(problem, lambda p: reference_solve(p, rf, re, **kw), ("tvec", "points2D", "points3D")):
+        if not same_stop(s, result) or abs(s.final_cost - result.final_cost) > 1e-7 * result.final_cost:
             return False
     return True
 

@@ -10,10 +10,10 @@ product:
     Jacobian of Ceres' QuaternionManifold; refined intrinsics are a subset;
   * CauchyLoss rho and rho'; the Corrector takes the rho'' <= 0 branch, so r
     and J are scaled by sqrt(rho');
-  * a dense Levenberg-Marquardt with Ceres 2.1 TrustRegionMinimizer semantics
-    (the radius rules of rig_reference.RigProblem.solve) plus the gradient,
-    parameter and function tolerance stops and the limit of 5 consecutive
-    invalid steps; it returns the (valid, successful, ended) trace.
+  * the dense Levenberg-Marquardt of lm_reference (Ceres 2.1
+    TrustRegionMinimizer semantics, the gradient, parameter and function
+    tolerance stops, 5 consecutive invalid steps); it returns the (valid,
+    successful, ended) trace.
 
 quat_product and unit_quat_rotate are restated here over torch tensors (the
 numpy ones of rig_reference cannot carry a gradient); test_generalized_pose
@@ -25,9 +25,10 @@ import numpy as np
 import torch
 
 import camera_model_ref as cm
+import lm_reference as lm
 import rig_reference as rr
+from lm_reference import CONVERGENCE, FAILURE, NO_CONVERGENCE  # noqa: F401
 
-CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2
 F64 = torch.float64
 
 
@@ -171,101 +172,29 @@ class Problem:
                 cams[c][i] += delta[self.off[c] + j]
         return q, t, cams
 
-    def _ambient(self, q, t, cams):
+    def ambient(self, q=None, t=None, cams=None):
+        q = self.q if q is None else q
+        t = self.t if t is None else t
+        cams = self.cams if cams is None else cams
         return np.concatenate([q, t] + [cams[c] for c in self.used if self.idx[c]])
 
+    def accept(self, q, t, cams):
+        self.q, self.t, self.cams = q, t, cams
+
     def solve(self, gradient_tolerance=1.0, max_num_iterations=100, function_tolerance=1e-6,
-              parameter_tolerance=1e-8, max_num_consecutive_invalid_steps=5, initial_trust_region_radius=1e4,
-              min_relative_decrease=1e-3):
+              parameter_tolerance=1e-8, **kw):
+        """lm_reference.minimize with RefineAbsolutePose's defaults."""
         N = len(self.xy)
 
-        def result(initial, final, ns, nu, term, trace):
-            return Result(self.q.copy(), self.t.copy(), [c.copy() for c in self.cams], initial, final, ns, nu, term,
-                          trace, 2 * N, self.n if N else 0)
+        def result(s):
+            return Result(self.q.copy(), self.t.copy(), [c.copy() for c in self.cams], *s, 2 * N, self.n if N else 0)
 
         if N == 0:
-            return result(0.0, 0.0, 0, 0, CONVERGENCE, [])
-        r, J, x_cost = self.jacobian()
-        initial = x_cost
-        if not np.isfinite(x_cost):
-            return result(initial, x_cost, 0, 0, FAILURE, [])
-        scale = 1.0 / (1.0 + np.sqrt((J * J).sum(0)))  # Jacobi scaling, fixed at iteration 0
-        radius, decrease_factor = initial_trust_region_radius, 2.0
-        ns = nu = invalid = iteration = 0
-        last_successful, trace, term = True, [], NO_CONVERGENCE
-        while True:
-            if iteration >= max_num_iterations:
-                term = NO_CONVERGENCE
-                break
-            if last_successful:
-                g = J.T @ r
-                qn, tn, cn = self.plus(-g)
-                if np.abs(self._ambient(self.q, self.t, self.cams) - self._ambient(qn, tn, cn)).max() <= \
-                        gradient_tolerance:
-                    term = CONVERGENCE
-                    break
-            if radius <= 1e-32:
-                term = CONVERGENCE
-                break
-            iteration += 1
-            Js = J * scale
-            diag = np.clip((Js * Js).sum(0), 1e-6, 1e32)
-            A = Js.T @ Js + np.diag(diag / radius)
-            ok = True
-            try:
-                L = np.linalg.cholesky(A)
-                y = np.linalg.solve(L.T, np.linalg.solve(L, -(Js.T @ r)))
-            except np.linalg.LinAlgError:
-                ok = False
-            model_change = 0.0
-            if ok:
-                delta = y * scale
-                mr = J @ delta
-                model_change = -mr @ (r + mr / 2)
-                ok = bool(np.isfinite(model_change) and model_change > 0)
-            if not ok:
-                invalid += 1
-                nu += 1
-                last_successful = False
-                radius /= decrease_factor
-                decrease_factor *= 2
-                end = invalid > max_num_consecutive_invalid_steps
-                trace.append((0, 0, int(end)))
-                if end:
-                    term = FAILURE
-                    break
-                continue
-            invalid = 0
-            cq, ct, cc = self.plus(delta)
-            cand_cost = self.cost(cq, ct, cc)
-            x_amb = self._ambient(self.q, self.t, self.cams)
-            step_norm = np.linalg.norm(x_amb - self._ambient(cq, ct, cc))
-            cost_change = x_cost - cand_cost
-            if step_norm <= parameter_tolerance * (np.linalg.norm(x_amb) + parameter_tolerance) or \
-                    abs(cost_change) <= function_tolerance * x_cost:
-                nu += 1
-                term = CONVERGENCE
-                trace.append((1, 0, 1))
-                break
-            rel = cost_change / model_change
-            if np.isfinite(cand_cost) and rel > min_relative_decrease:
-                ns += 1
-                last_successful = True
-                x_cost = cand_cost
-                self.q, self.t, self.cams = cq, ct, cc
-                radius = min(1e16, radius / max(1.0 / 3.0, 1.0 - (2.0 * rel - 1.0) ** 3))
-                decrease_factor = 2.0
-                r, J, _ = self.jacobian()
-                trace.append((1, 1, 0))
-            else:
-                nu += 1
-                last_successful = False
-                radius /= decrease_factor
-                decrease_factor *= 2
-                trace.append((1, 0, 0))
-        if term == FAILURE:
+            return result(lm.Solve(0.0, 0.0, 0, 0, CONVERGENCE, []))
+        s = lm.minimize(self, gradient_tolerance, max_num_iterations, function_tolerance, parameter_tolerance, **kw)
+        if s.termination_type == FAILURE and s.trace:  # after iterations; a non-finite initial cost is reported
             raise AssertionError("the reference does not restore parameters after FAILURE: unexpected here")
-        return result(initial, x_cost, ns, nu, term, trace)
+        return result(s)
 
     def covariance(self):
         """inv(J'J)[:6, :6] of the loss-corrected Jacobian at the current point."""

@@ -8,6 +8,7 @@ import numpy as np
 
 import mi_ba
 import oracle
+from estimator_testing import qmul, quat, same_stop, ulp_solves
 
 TRUE_PARAMS = {
     mi_ba.SIMPLE_RADIAL: [1200.0, 500.0, 500.0, 0.02],
@@ -21,20 +22,13 @@ START_OFFSET = {
 }
 
 
-def _quat(axis_angle):
-    a = np.linalg.norm(axis_angle)
-    if a == 0:
-        return np.array([1.0, 0, 0, 0])
-    return np.concatenate([[np.cos(a / 2)], np.sin(a / 2) * axis_angle / a])
-
-
 def make_problem(model, n, seed, outlier_fraction=0.1, outlier_px=40.0, noise_px=0.5):
     """n correspondences of a camera 5 units in front of a unit cloud, pixel
     noise, round(outlier_fraction n) gross outliers moved by outlier_px, and a
     start off the true pose and intrinsics."""
     rng = np.random.default_rng(seed)
     prm = np.array(TRUE_PARAMS[model])
-    q = _quat(rng.normal(size=3) * 0.1)
+    q = quat(rng.normal(size=3) * 0.1)
     t = np.array([0.1, -0.2, 5.0]) + rng.normal(size=3) * 0.1
     X = rng.uniform(-1.0, 1.0, size=(n, 3)) * [1.5, 1.5, 1.0]
     R = mi_ba.quat_to_rot(q)
@@ -46,8 +40,7 @@ def make_problem(model, n, seed, outlier_fraction=0.1, outlier_px=40.0, noise_px
         who = rng.choice(n, n_out, replace=False)
         ang = rng.uniform(0, 2 * np.pi, n_out)
         xy[who] += outlier_px * np.stack([np.cos(ang), np.sin(ang)], axis=1)
-    dq = _quat(rng.normal(size=3) * 0.01)
-    q0 = np.array([dq[0] * q[0] - dq[1:] @ q[1:], *(dq[0] * q[1:] + q[0] * dq[1:] + np.cross(dq[1:], q[1:]))])
+    q0 = qmul(quat(rng.normal(size=3) * 0.01), q)
     q0 /= np.linalg.norm(q0)
     t0 = t + rng.normal(size=3) * 0.03
     return mi_ba.PoseProblem(model, prm + START_OFFSET[model], q0, t0, xy, X)
@@ -71,29 +64,14 @@ def oracle_solve(problem, **kw):
     return s, trace[trace[:, 0] >= 0], sc
 
 
-def ulp_perturbed(problem, rng):
-    """The problem with every input coordinate moved by -1, 0 or +1 ulp."""
-    b = problem.copy()
-    for name in ("tvec", "points2D", "points3D"):
-        a = getattr(b, name)
-        s = rng.choice([-1, 0, 1], a.shape).astype(float)
-        a[:] = np.where(s == 0, a, np.nextafter(a, a + s))
-    return b
-
-
 def is_stable(problem, summary, **kw):
     """The oracle's step counts survive ulp perturbations of the inputs: its
     stop is not decided by rounding (tests/test_lm_semantics.py); and its own
     final cost moves by less than 1e-7 relative under them, a tenth of the
     parity bound (an exactly fitted problem ends at a cost near zero whose
     relative value is rounding)."""
-    rng = np.random.default_rng(7)
-    for _ in range(3):
-        s, _, _ = oracle_solve(ulp_perturbed(problem, rng), **kw)
-        if (s.num_successful_steps, s.num_unsuccessful_steps, s.termination_type) != (
-                summary.num_successful_steps, summary.num_unsuccessful_steps, summary.termination_type):
-            return False
-        if abs(s.final_cost - summary.final_cost) > 1e-7 * summary.final_cost:
+    for s, _, _ in ulp_solves(problem, lambda p: oracle_solve(p, **kw), ("tvec", "points2D", "points3D")):
+        if not same_stop(s, summary) or abs(s.final_cost - summary.final_cost) > 1e-7 * summary.final_cost:
             return False
     return True
 

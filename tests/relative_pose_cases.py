@@ -34,20 +34,10 @@ import numpy as np
 
 import mi_ba
 import relative_pose_reference as rref
+from estimator_testing import qmul, quat, same_stop, ulp_solves
 
 NOISE = 0.5 / 1200
 OUTLIER = 40.0 / 1200
-
-
-def quat(axis_angle):
-    a = np.linalg.norm(axis_angle)
-    if a == 0:
-        return np.array([1.0, 0, 0, 0])
-    return np.concatenate([[np.cos(a / 2)], np.sin(a / 2) * np.asarray(axis_angle) / a])
-
-
-def qmul(z, w):
-    return np.array([z[0] * w[0] - z[1:] @ w[1:], *(z[0] * w[1:] + w[0] * z[1:] + np.cross(z[1:], w[1:]))])
 
 
 def make_problem(n, seed, direction="random", outlier_fraction=0.1, baseline=1.0):
@@ -102,28 +92,14 @@ def median_initial_residual(pr):
     return float(np.median(r))
 
 
-def ulp_perturbed(problem, rng):
-    """The problem with every input coordinate moved by -1, 0 or +1 ulp."""
-    b = problem.copy()
-    for name in ("tvec", "points1", "points2"):
-        a = getattr(b, name)
-        s = rng.choice([-1, 0, 1], a.shape).astype(float)
-        a[:] = np.where(s == 0, a, np.nextafter(a, a + s))
-    return b
-
-
 def stability(problem, result, scale, **kw):
     """(stable, cost spread, q / t spread): pose_cases.is_stable's question
     asked of the reference (do its step counts and stop survive ulp
     perturbations of the inputs?) and the largest change of its final cost
     (absolute) and of q, t under them."""
-    rng = np.random.default_rng(7)
     stable, dcost, dqt = True, 0.0, 0.0
-    for _ in range(3):
-        s = reference_solve(ulp_perturbed(problem, rng), scale, **kw)
-        if (s.num_successful_steps, s.num_unsuccessful_steps, s.termination_type) != (
-                result.num_successful_steps, result.num_unsuccessful_steps, result.termination_type):
-            stable = False
+    for s in ulp_solves(problem, lambda p: reference_solve(p, scale, **kw), ("tvec", "points1", "points2")):
+        stable = stable and same_stop(s, result)
         dcost = max(dcost, abs(s.final_cost - result.final_cost))
         dqt = max(dqt, float(np.abs(s.qvec - result.qvec).max()), float(np.abs(s.tvec - result.tvec).max()))
     return stable, dcost, dqt

@@ -11,7 +11,7 @@ product:
     SphereManifold<3> (3 x 2), both restated here;
   * CauchyLoss rho and rho'; the Corrector takes the rho'' <= 0 branch, so r
     and J are scaled by sqrt(rho');
-  * the dense Levenberg-Marquardt of generalized_pose_reference (Ceres 2.1
+  * the dense Levenberg-Marquardt of lm_reference (Ceres 2.1
     TrustRegionMinimizer semantics, the gradient, parameter and function
     tolerance stops, 5 consecutive invalid steps); it returns the (valid,
     successful, ended) trace.
@@ -23,9 +23,10 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
+import lm_reference as lm
 import rig_reference as rr
+from lm_reference import CONVERGENCE, FAILURE, NO_CONVERGENCE  # noqa: F401
 
-CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2
 EPS = np.finfo(np.float64).eps
 
 
@@ -160,98 +161,28 @@ class Problem:
     def plus(self, delta):
         return rr.quat_plus(self.q, delta[0:3]), sphere_plus(self.t, delta[3:5])
 
+    def ambient(self, q=None, t=None):
+        return np.concatenate([self.q if q is None else q, self.t if t is None else t])
+
+    def accept(self, q, t):
+        self.q, self.t = q, t
+
     def solve(self, max_num_iterations=50, function_tolerance=1e-6, gradient_tolerance=1e-10,
-              parameter_tolerance=1e-8, max_num_consecutive_invalid_steps=5, initial_trust_region_radius=1e4,
-              min_relative_decrease=1e-3):
+              parameter_tolerance=1e-8, **kw):
+        """lm_reference.minimize with ceres::Solver::Options' defaults."""
         N = len(self.x1)
 
-        def result(initial, final, ns, nu, term, trace):
-            return Result(self.q.copy(), self.t.copy(), initial, final, ns, nu, term, trace, N, 5 if N else 0)
+        def result(s):
+            return Result(self.q.copy(), self.t.copy(), *s, N, 5 if N else 0)
 
         if N == 0:
-            return result(0.0, 0.0, 0, 0, CONVERGENCE, [])
-        with np.errstate(all="ignore"):
-            r, J, x_cost = self.jacobian()
-        initial = x_cost
-        if not np.isfinite(x_cost):
-            return result(initial, x_cost, 0, 0, FAILURE, [])
-        scale = 1.0 / (1.0 + np.sqrt((J * J).sum(0)))  # Jacobi scaling, fixed at iteration 0
-        radius, decrease_factor = initial_trust_region_radius, 2.0
-        ns = nu = invalid = iteration = 0
-        last_successful, trace, term = True, [], NO_CONVERGENCE
+            return result(lm.Solve(0.0, 0.0, 0, 0, CONVERGENCE, []))
         q0, t0 = self.q.copy(), self.t.copy()
-        while True:
-            if iteration >= max_num_iterations:
-                term = NO_CONVERGENCE
-                break
-            if last_successful:
-                qn, tn = self.plus(-(J.T @ r))
-                if np.abs(np.concatenate([self.q - qn, self.t - tn])).max() <= gradient_tolerance:
-                    term = CONVERGENCE
-                    break
-            if radius <= 1e-32:
-                term = CONVERGENCE
-                break
-            iteration += 1
-            Js = J * scale
-            diag = np.clip((Js * Js).sum(0), 1e-6, 1e32)
-            A = Js.T @ Js + np.diag(diag / radius)
-            ok = True
-            try:
-                L = np.linalg.cholesky(A)
-                y = np.linalg.solve(L.T, np.linalg.solve(L, -(Js.T @ r)))
-            except np.linalg.LinAlgError:
-                ok = False
-            model_change = 0.0
-            if ok:
-                delta = y * scale
-                mr = J @ delta
-                model_change = -mr @ (r + mr / 2)
-                ok = bool(np.isfinite(model_change) and model_change > 0)
-            if not ok:
-                invalid += 1
-                nu += 1
-                last_successful = False
-                radius /= decrease_factor
-                decrease_factor *= 2
-                end = invalid > max_num_consecutive_invalid_steps
-                trace.append((0, 0, int(end)))
-                if end:
-                    term = FAILURE
-                    break
-                continue
-            invalid = 0
-            cq, ct = self.plus(delta)
-            with np.errstate(all="ignore"):
-                cand_cost = self.cost(cq, ct)
-            x_amb = np.concatenate([self.q, self.t])
-            step_norm = np.linalg.norm(x_amb - np.concatenate([cq, ct]))
-            cost_change = x_cost - cand_cost
-            if step_norm <= parameter_tolerance * (np.linalg.norm(x_amb) + parameter_tolerance) or \
-                    abs(cost_change) <= function_tolerance * x_cost:
-                nu += 1
-                term = CONVERGENCE
-                trace.append((1, 0, 1))
-                break
-            rel = cost_change / model_change
-            if np.isfinite(cand_cost) and rel > min_relative_decrease:
-                ns += 1
-                last_successful = True
-                x_cost = cand_cost
-                self.q, self.t = cq, ct
-                radius = min(1e16, radius / max(1.0 / 3.0, 1.0 - (2.0 * rel - 1.0) ** 3))
-                decrease_factor = 2.0
-                r, J, _ = self.jacobian()
-                trace.append((1, 1, 0))
-            else:
-                nu += 1
-                last_successful = False
-                radius /= decrease_factor
-                decrease_factor *= 2
-                trace.append((1, 0, 0))
-        if term == FAILURE:  # Ceres leaves the parameter blocks as they were given
+        with np.errstate(all="ignore"):  # an evaluation may overflow on the way to a rejected step
+            s = lm.minimize(self, gradient_tolerance, max_num_iterations, function_tolerance, parameter_tolerance, **kw)
+        if s.termination_type == FAILURE:  # Ceres leaves the parameter blocks as they were given
             self.q, self.t = q0, t0
-        return result(initial, x_cost, ns, nu, term, trace)
+        return result(s)
 
 
 def essential_matrix(q, t):

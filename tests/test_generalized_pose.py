@@ -25,7 +25,6 @@ torch tensors, because rig_reference's numpy versions cannot carry a gradient;
 the first test below pins the restatements to them bit for bit."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -36,6 +35,7 @@ import mi_ba
 import oracle
 import pose_cases as pc
 import rig_reference as rr
+from estimator_testing import gpu_sequence, hexes, oracle_sequence, run_program
 
 M = mi_ba
 
@@ -51,14 +51,6 @@ def as_rig(pr):
                                     np.zeros((1, 3)), pr.qvec.copy(), pr.tvec.copy(), pr.points2D.copy(),
                                     pr.points3D.copy(), np.zeros(n, np.int32),
                                     None if pr.inlier_mask is None else pr.inlier_mask.copy())
-
-
-def oracle_sequence(trace):
-    return [(int(v), int(s), int(e)) for v, s, _, e in trace]
-
-
-def gpu_sequence(row):
-    return [(int(b) & 1, (int(b) >> 1) & 1, (int(b) >> 2) & 1) for b in row if b != 0xFF]
 
 
 # --------------------------------------------------------------------------- CPU: the reference
@@ -545,18 +537,9 @@ def test_edge_semantics(gpu):
 
 
 # --------------------------------------------------------------------------- facade (C++)
-CPP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cpp")
-
-
 def run_cpp(*args):
     """tests/cpp/generalized_pose_refinement_test.cc through include/colmap_amd/pose.h."""
-    subprocess.run(["make", "-C", CPP, "-f", "Makefile.gpose"], check=True, capture_output=True)
-    out = subprocess.run([os.path.join(CPP, "generalized_pose_refinement_test"), *args], capture_output=True, text=True,
-                         timeout=300)
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "0 failure(s)" in out.stdout
-    return out.stdout
+    return run_program("generalized_pose_refinement_test", *args)
 
 
 def test_generalized_pose_facade_host():
@@ -566,7 +549,7 @@ def test_generalized_pose_facade_host():
 
 def write_problem(pr, path):
     """The text form generalized_pose_refinement_test.cc reads: hex floats."""
-    h = lambda xs: " ".join(float(x).hex() for x in np.asarray(xs, np.float64).reshape(-1))
+    h = hexes
     mask = np.ones(len(pr.camera_idxs), np.uint8) if pr.inlier_mask is None else pr.inlier_mask
     with open(path, "w") as f:
         f.write(f"{len(pr.camera_models)}\n")

@@ -9,8 +9,6 @@ SIMPLE_RADIAL, OPENCV and OPENCV_FISHEYE.  The oracle has no OPENCV_FISHEYE:
 those problems are checked against the existing GPU solver (mi_ba.solve) on
 the equivalent scene."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,6 +16,7 @@ import pytest
 import mi_ba
 import oracle
 import pose_cases as pc
+from estimator_testing import gpu_sequence, oracle_sequence, run_program
 
 
 def rel(a, b):
@@ -121,15 +120,6 @@ def same_bits(res_a, i, res_b, j):
             and res_a.summaries[i].num_successful_steps == res_b.summaries[j].num_successful_steps
             and res_a.summaries[i].num_unsuccessful_steps == res_b.summaries[j].num_unsuccessful_steps
             and res_a.usable[i] == res_b.usable[j])
-
-
-def oracle_sequence(trace):
-    """(valid, successful, ended) per iteration of the oracle trace."""
-    return [(int(v), int(s), int(e)) for v, s, _, e in trace]
-
-
-def gpu_sequence(row):
-    return [(int(b) & 1, (int(b) >> 1) & 1, (int(b) >> 2) & 1) for b in row if b != 0xFF]
 
 
 @pytest.mark.gpu
@@ -340,17 +330,9 @@ def test_agrees_with_the_existing_gpu_solver(gpu, model):
 
 
 # --------------------------------------------------------------------------- facade (C++)
-CPP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cpp")
-
-
 def run_cpp(mode):
     """tests/cpp/pose_refinement_test.cc through include/colmap_amd/pose.h."""
-    subprocess.run(["make", "-C", CPP, "-f", "Makefile.pose"], check=True, capture_output=True)
-    out = subprocess.run([os.path.join(CPP, "pose_refinement_test"), mode], capture_output=True, text=True, timeout=300)
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "0 failure(s)" in out.stdout
-    return out.stdout
+    return run_program("pose_refinement_test", mode)
 
 
 def test_pose_facade_host():

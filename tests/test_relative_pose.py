@@ -18,7 +18,6 @@ ulp-perturbed inputs where that is larger (relative_pose_cases: on the
 committed seeds it never is)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -26,21 +25,13 @@ import pytest
 import mi_ba
 import relative_pose_cases as rc
 import relative_pose_reference as rref
+from estimator_testing import gpu_sequence, hexes, make, run_program
 
 M = mi_ba
-CPP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cpp")
 
 
 def opts(**kw):
     return M.default_relative_pose_options(**kw)
-
-
-def gpu_sequence(row):
-    return [(int(b) & 1, (int(b) >> 1) & 1, (int(b) >> 2) & 1) for b in row if b != 0xFF]
-
-
-def hexes(xs):
-    return " ".join(float(x).hex() for x in np.asarray(xs, np.float64).reshape(-1))
 
 
 def write_problem(pr, path):
@@ -49,19 +40,6 @@ def write_problem(pr, path):
         f.write(f"{hexes(pr.qvec)} {hexes(pr.tvec)}\n{len(pr.points1)}\n")
         for a, b in zip(pr.points1, pr.points2):
             f.write(f"{hexes(a)} {hexes(b)}\n")
-
-
-def make(target):
-    subprocess.run(["make", "-C", CPP, "-f", "Makefile.rpose", target], check=True, capture_output=True)
-    return os.path.join(CPP, target)
-
-
-def run_program(target, *args):
-    out = subprocess.run([make(target), *args], capture_output=True, text=True, timeout=300)
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "0 failure(s)" in out.stdout
-    return out.stdout
 
 
 def scaled_difference(got, want):

@@ -22,8 +22,8 @@ committed seeds none is.
 CPU tests run the host build of the block header (tests/cpp/
 triangulation_block_test.cc) and the facade's host mode; GPU tests the device."""
 import ctypes as C
+import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -31,9 +31,10 @@ import pytest
 import mi_ba
 import triangulation_cases as tc
 import triangulation_reference as tref
+from estimator_testing import hexes, make, run_program
 
 M = mi_ba
-CPP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cpp")
+run_program = functools.partial(run_program, timeout=600)
 INT64_MAX = 2 ** 63 - 1
 
 # the categories of the parity comparison: every one must keep a stable case
@@ -47,23 +48,6 @@ CATEGORIES = {
     "min_num_trials": ["len20_min150"],
     "failing": list(tc.FAILING),
 }
-
-
-def hexes(xs):
-    return " ".join(float(x).hex() for x in np.asarray(xs, np.float64).reshape(-1))
-
-
-def make(target):
-    subprocess.run(["make", "-C", CPP, "-f", "Makefile.tri", target], check=True, capture_output=True)
-    return os.path.join(CPP, target)
-
-
-def run_program(target, *args):
-    out = subprocess.run([make(target), *args], capture_output=True, text=True, timeout=600)
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "0 failure(s)" in out.stdout
-    return out.stdout
 
 
 def option_key(o):

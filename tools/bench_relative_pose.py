@@ -59,33 +59,15 @@ class AbsoluteCall:
     def __init__(self, problems):
         n = len(problems)
         self.o = mi_ba.default_pose_refine_options(refine_focal_length=0, refine_extra_params=0)
-        cnt = [len(p.points2D) for p in problems]
-        self.obs_off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-        self.p2 = np.ascontiguousarray(np.concatenate([p.points2D for p in problems]))
-        self.p3 = np.ascontiguousarray(np.concatenate([p.points3D for p in problems]))
-        self.models = np.array([p.camera_model for p in problems], np.int32)
-        self.cam_off = np.concatenate([[0], np.cumsum([len(p.camera_params) for p in problems])]).astype(np.int64)
-        self.c0 = np.ascontiguousarray(np.concatenate([p.camera_params for p in problems]))
-        self.q0 = np.ascontiguousarray(np.array([p.qvec for p in problems]))
-        self.t0 = np.ascontiguousarray(np.array([p.tvec for p in problems]))
-        self.cams, self.q, self.t = self.c0.copy(), self.q0.copy(), self.t0.copy()
-        b = self.b = mi_ba.PoseBatch()
-        b.num_problems = n
-        b.obs_offsets = self.obs_off.ctypes.data_as(mi_ba._i64p)
-        b.points2D = self.p2.ctypes.data_as(mi_ba._dp)
-        b.points3D = self.p3.ctypes.data_as(mi_ba._dp)
-        b.camera_model_ids = self.models.ctypes.data_as(mi_ba._i32p)
-        b.camera_param_offsets = self.cam_off.ctypes.data_as(mi_ba._i64p)
-        b.camera_params = self.cams.ctypes.data_as(mi_ba._dp)
-        b.qvec = self.q.ctypes.data_as(mi_ba._dp)
-        b.tvec = self.t.ctypes.data_as(mi_ba._dp)
+        self.a = mi_ba._PoseArrays(problems)
+        self.c0, self.q0, self.t0 = self.a.cams.copy(), self.a.q.copy(), self.a.t.copy()
         self.st, self.us, self.sums = np.zeros(n, np.int32), np.zeros(n, np.int32), (mi_ba.Summary * n)()
 
     def __call__(self):
-        self.cams[:], self.q[:], self.t[:] = self.c0, self.q0, self.t0
+        self.a.cams[:], self.a.q[:], self.a.t[:] = self.c0, self.q0, self.t0
         t = time.perf_counter()
         rc_ = mi_ba.load().mi_ba_refine_absolute_pose_batch(
-            C.byref(self.o), C.byref(self.b), self.st.ctypes.data_as(mi_ba._i32p), C.cast(self.sums, C.c_void_p),
+            C.byref(self.o), C.byref(self.a.batch), self.st.ctypes.data_as(mi_ba._i32p), C.cast(self.sums, C.c_void_p),
             self.us.ctypes.data_as(mi_ba._i32p))
         dt = time.perf_counter() - t
         assert rc_ == 0 and np.all(self.us == 1)

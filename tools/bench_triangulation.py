@@ -125,8 +125,7 @@ class Call:
 def host(s, o, path):
     """The host build of the block header on the same batch: (best seconds, per-track outputs)."""
     exe = os.path.join(ROOT, "tests", "cpp", "triangulation_block_test")
-    subprocess.run(["make", "-C", os.path.dirname(exe), "-f", "Makefile.tri", "triangulation_block_test"], check=True,
-                   capture_output=True)
+    subprocess.run(["make", "-C", os.path.dirname(exe), "triangulation_block_test"], check=True, capture_output=True)
     prm8 = np.zeros((len(s["cams"]), 8))
     for c, (_, prm) in enumerate(s["cams"]):
         prm8[c, :len(prm)] = prm
