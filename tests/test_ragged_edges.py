@@ -152,19 +152,38 @@ def reference_options(opts):
 _REFERENCE = {}
 
 
-def oracle_step(opts, sc):
+def oracle_step(opts, sc, sem=None):
     """(summary, {iteration: (valid, successful, cg)}, solved copy) of the
-    oracle's LM on a copy of sc — computed once per (options, scene), shared
-    and left unchanged."""
+    oracle's LM on a copy of sc (with the semantic input sem, if any) —
+    computed once per (options, scene, semantic input), shared and left
+    unchanged."""
     ref = reference_options(opts)
     h = hashlib.sha1(bytes(ref))
-    for name in ("obs_xy", "obs_image", "obs_point", "image_camera", "camera_params", "point_config"):
-        a = getattr(sc, name)
-        h.update(b"-" if a is None else np.ascontiguousarray(a).tobytes())
+
+    def feed(a):
+        # shape and type too: back-to-back arrays must not run into each other
+        if a is None:
+            h.update(b"-")
+        else:
+            a = np.ascontiguousarray(a)
+            h.update(f"|{a.dtype.str}{a.shape}|".encode())
+            h.update(a.tobytes())
+
+    for name in ("obs_xy", "obs_image", "obs_point", "image_camera", "camera_params", "point_config", "qvec", "tvec",
+                 "xyz", "camera_models", "camera_constant", "image_constant_pose", "image_constant_tvec"):
+        feed(getattr(sc, name))
+    if sem is None:
+        h.update(b"no semantic input")
+    else:
+        feed(np.asarray(sem.pairs, np.int32).reshape(-1, 2))
+        for maps in (sem.depth, sem.label):
+            for plane in maps:
+                feed(np.asarray(plane, np.float32))
+        feed(np.array([sem.pixel_step, sem.depth_error_threshold, sem.numeric_relative_step_size], np.float64))
     key = (sc.camera_model, h.digest())
     if key not in _REFERENCE:
         o = sc.copy()
-        s, tr = oracle.solve_traced(ref, o)
+        s, tr = oracle.solve_traced(ref, o, sem)
         _REFERENCE[key] = (s, trace_rows(tr), o)
     return _REFERENCE[key]
 
@@ -360,13 +379,15 @@ def test_one_dropped_observation_moves_the_oracle_step(kind):
 # ---------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------
-def assert_step_parity(opts, scene, tuning=None):
+def assert_step_parity(opts, scene, tuning=None, sem=None, gpu_solve=gpu_traced):
     """The GPU LM (through a Context, tuning applied before the solve) against
-    the oracle's on copies of the scene; returns the largest step ratio."""
-    s_o, rows_o, o = oracle_step(opts, scene)
+    the oracle's on copies of the scene, with the semantic input sem if given;
+    returns the largest step ratio.  gpu_solve: a stand-in for gpu_traced with
+    its signature (a caller that also reads the context's launch counts)."""
+    s_o, rows_o, o = oracle_step(opts, scene, sem)
     g = scene.copy()
     try:
-        s_g, rec = gpu_traced(opts, g, tuning=tuning)
+        s_g, rec = gpu_solve(opts, g, sem, tuning=tuning)
     except mi_ba.MiBaError as e:
         if str(e).startswith("set_tuning"):
             pytest.skip(f"{tuning}: refused by this build (tools build only): {e}")
