@@ -39,6 +39,9 @@
  *                              <- EstimateTriangulation (src/estimators/triangulation.cc:132-160),
  *                                 many tracks per call; TriangulatePoints and
  *                                 CalculateTriangulationAngles (src/base/triangulation.cc)
+ *   mi_ba_estimate_absolute_pose_batch
+ *                              <- EstimateAbsolutePose (src/estimators/pose.cc:50-158), many
+ *                                 images or focal-length hypotheses per call
  *   mi_ba_semantic (struct)   <- SemanticBundleAdjustmentOptions depth/semantic maps
  *                                 (src/optim/semantic_bundle_adjustment.h:53-140,
  *                                 semantic_bundle_adjustment.cc:699-906,1021-1068)
@@ -1122,6 +1125,120 @@ int32_t mi_ba_triangulation_lds_capacity(void);
 mi_ba_status mi_ba_triangulate_points(const double* proj_matrix1, const double* proj_matrix2, int64_t m,
                                       const double* points1, const double* points2, const double* proj_center1,
                                       const double* proj_center2, int32_t device, double* xyz, double* angles);
+
+/* --- batched robust absolute pose --------------------------------------------
+ * Additive entry points (MI_BA_ABI_VERSION stays 4).
+ * EstimateAbsolutePose (src/estimators/pose.cc:50-158, called from
+ * IncrementalMapper::RegisterNextImage before RefineAbsolutePose): per focal
+ * length hypothesis a LORANSAC<P3PEstimator, EPNPEstimator,
+ * InlierSupportMeasurer, RandomSampler> on the image points normalised under
+ * the scaled camera, with max_error / mean focal length as the threshold.
+ * Matched decision for decision: the support comparison, the local
+ * optimisation (only with more than three and at least four inliers, at most
+ * 10 recursions on the inlier set of the model evaluated last, each accepted
+ * only if it compares better, ended when the inlier count did not grow),
+ * ComputeNumTrials for three samples with its three early returns, the abort
+ * test after every model of a trial (never for a trial without models), the
+ * one more counted trial after an abort, the constructor's cap of
+ * max_num_trials by min_inlier_ratio, success iff the best support has three
+ * inliers and neither qvec nor tvec holds a NaN.
+ *
+ * Three build deviations:
+ *  - The sampler.  RandomSampler draws from a thread-local std::mt19937
+ *    through std::uniform_int_distribution, which is implementation-defined
+ *    and shared with whatever else runs on the thread; there is no reference
+ *    stream to equal.  Here trial t of a problem with seed s takes the first
+ *    three steps of a Fisher-Yates shuffle of the identity permutation,
+ *    j_i = i + mulhi64(r_i, n - i), r_i = mix(mix(mix(s) ^ t) ^ i) with
+ *    splitmix64's finaliser as mix (z += 0x9E3779B97F4A7C15 first).  The
+ *    multiply-high reduction is biased by at most n / 2^64.  Same
+ *    distribution as RandomSampler::Sample; stateless, so a problem gives the
+ *    same result at every batch position and alone.
+ *  - The order of a trial's models.  P3P yields up to four; each improving one
+ *    triggers a local optimisation, so their order matters.  The reference
+ *    takes them in the order Eigen's EigenSolver returns the companion
+ *    matrix's eigenvalues; here they are taken in ascending order of the root
+ *    x.  (std::pow(r, 3) of ComputeNumTrials is r * r * r.)
+ *  - The orientation of EPnP's control points.  The pose EPnP returns depends,
+ *    at the level of the data's noise, on the signs of the three principal
+ *    axes that span the control points (c_i and 2 c_0 - c_i give different
+ *    barycentric coordinates and a different M).  The reference takes the
+ *    signs JacobiSVD returns; here an axis is oriented so that its component
+ *    of the largest magnitude is positive.
+ *
+ * The defaults are those of RANSACOptions (optim/ransac.h:47-66); max_error
+ * has none (0, which Check() refuses).  max_num_trials: size_t's maximum is
+ * INT64_MAX here. */
+typedef struct mi_ba_absolute_pose_estimation_options {
+  double max_error;                  /* pixels; no default */
+  double min_inlier_ratio;           /* default 0.1 */
+  double confidence;                 /* default 0.99 */
+  double dyn_num_trials_multiplier;  /* default 3.0 */
+  int64_t min_num_trials;            /* default 0 */
+  int64_t max_num_trials;            /* default INT64_MAX */
+  uint64_t seed;                     /* default 0; the sampler's, for problems without their own */
+  int32_t device;                    /* HIP device ordinal, default 0 */
+} mi_ba_absolute_pose_estimation_options;
+
+/* Zeroes the struct (padding included), then sets the defaults above. */
+void mi_ba_default_absolute_pose_estimation_options(mi_ba_absolute_pose_estimation_options* options);
+
+/* A batch as a struct of arrays.  Correspondence set s owns the rows
+ * set_offsets[s] .. set_offsets[s + 1) of points2D (pixels) and points3D.
+ * Problem k estimates the pose of set set_index[k] under camera
+ * camera_index[k] with its focal parameters scaled by focal_length_factor[k]
+ * (NULL: 1) and the sampler seeded with seed[k] (NULL: options.seed); the 31
+ * hypotheses of a focal sweep thus share one copy of their correspondences.
+ * Cameras have the layout of the pose entry points. */
+typedef struct mi_ba_absolute_pose_estimation_batch {
+  int32_t num_sets;
+  const int64_t* set_offsets;          /* [num_sets + 1] */
+  const double* points2D;              /* [set_offsets[num_sets]][2] pixels */
+  const double* points3D;              /* [set_offsets[num_sets]][3] */
+  int32_t num_cameras;
+  const int32_t* camera_model_ids;     /* [num_cameras] MI_BA_* model id */
+  const int64_t* camera_param_offsets; /* [num_cameras + 1] */
+  const double* camera_params;
+  int32_t num_problems;
+  const int32_t* set_index;            /* [num_problems] */
+  const int32_t* camera_index;         /* [num_problems] */
+  const double* focal_length_factor;   /* nullable [num_problems] */
+  const uint64_t* seed;                /* nullable [num_problems] */
+} mi_ba_absolute_pose_estimation_batch;
+
+/* Estimates every problem of the batch in one launch (one wavefront per
+ * problem, the whole LO-RANSAC on the device; the 64 trials of a round are
+ * drawn, solved and scored together and committed in trial order).  Per
+ * problem k, always written: success[k], num_trials[k], num_inliers[k] (the
+ * best support's) and best_is_local[k]; on success only: proj_matrix[k] (row-major 3 x 4), qvec[k]
+ * (RotationMatrixToQuaternion of its rotation, w first), tvec[k] and the
+ * problem's part of inlier_mask.  The masks of the problems lie one after the
+ * other: problem k's starts at the sum of the sizes of the sets of problems
+ * 0 .. k - 1 and has one entry per correspondence of its set (1 = residual
+ * <= (max_error / mean focal)^2 under the best model).  A failed problem
+ * (fewer than three correspondences: 0 trials) leaves proj_matrix, qvec, tvec
+ * and its mask entries untouched; its three counters above are written all
+ * the same.  Outputs other than success are nullable.
+ * MI_BA_ERR_INVALID_ARGUMENT, before any device is touched, for what
+ * RANSACOptions::Check refuses (max_error <= 0, min_inlier_ratio or
+ * confidence outside [0, 1], min_num_trials > max_num_trials), a focal factor
+ * that is not positive and finite, a negative count, offsets that decrease, a
+ * set of more than INT32_MAX / 5 correspondences, a set or camera index out
+ * of range, a camera model outside the nine
+ * supported or whose parameter count does not fit, and a trial bound that
+ * stays at INT64_MAX after the constructor's cap (confidence 1 or
+ * min_inlier_ratio 0 without a max_num_trials): every device loop is bounded
+ * by that number.  Every sum runs in a fixed order without atomics: a problem
+ * gives the same bits on every run, at every position of a batch and alone. */
+mi_ba_status mi_ba_estimate_absolute_pose_batch(const mi_ba_absolute_pose_estimation_options* options,
+                                                const mi_ba_absolute_pose_estimation_batch* batch,
+                                                double* proj_matrix, double* qvec, double* tvec,
+                                                uint8_t* inlier_mask, int32_t* success, int64_t* num_trials,
+                                                int32_t* num_inliers, int32_t* best_is_local);
+
+/* Most correspondences of one problem that the kernel keeps resident in LDS;
+ * a longer problem keeps its normalised records in device memory.  Host only. */
+int32_t mi_ba_absolute_pose_lds_capacity(void);
 
 /* Per-kernel HIP-event timing on the context's stream (enabled with
  * mi_ba_set_timing).  name: "reproj_jacobian", "semantic_jacobian", ... */

@@ -44,6 +44,7 @@ _fp = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
 _u8p = C.POINTER(C.c_uint8)
+_u64p = C.POINTER(C.c_uint64)
 
 
 class IterationSummary(C.Structure):
@@ -364,6 +365,38 @@ class TriangulationBatch(C.Structure):
     ]
 
 
+class AbsolutePoseEstimationOptions(C.Structure):
+    """mi_ba_absolute_pose_estimation_options (the RANSACOptions of EstimateAbsolutePose and the sampler's seed)."""
+    _fields_ = [
+        ("max_error", C.c_double),
+        ("min_inlier_ratio", C.c_double),
+        ("confidence", C.c_double),
+        ("dyn_num_trials_multiplier", C.c_double),
+        ("min_num_trials", C.c_int64),
+        ("max_num_trials", C.c_int64),
+        ("seed", C.c_uint64),
+        ("device", C.c_int32),
+    ]
+
+
+class AbsolutePoseEstimationBatch(C.Structure):
+    _fields_ = [
+        ("num_sets", C.c_int32),
+        ("set_offsets", _i64p),
+        ("points2D", _dp),
+        ("points3D", _dp),
+        ("num_cameras", C.c_int32),
+        ("camera_model_ids", _i32p),
+        ("camera_param_offsets", _i64p),
+        ("camera_params", _dp),
+        ("num_problems", C.c_int32),
+        ("set_index", _i32p),
+        ("camera_index", _i32p),
+        ("focal_length_factor", _dp),
+        ("seed", _u64p),
+    ]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [
         ("camera_model", C.c_int32),
@@ -489,6 +522,13 @@ def load(path: str = LIB_PATH):
     lib.mi_ba_triangulation_lds_capacity.argtypes = []
     lib.mi_ba_triangulation_lds_capacity.restype = C.c_int32
     lib.mi_ba_triangulate_points.argtypes = [_dp, _dp, C.c_int64, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp]
+    lib.mi_ba_default_absolute_pose_estimation_options.argtypes = [C.POINTER(AbsolutePoseEstimationOptions)]
+    lib.mi_ba_default_absolute_pose_estimation_options.restype = None
+    lib.mi_ba_estimate_absolute_pose_batch.argtypes = [C.POINTER(AbsolutePoseEstimationOptions),
+                                                       C.POINTER(AbsolutePoseEstimationBatch), _dp, _dp, _dp, _u8p,
+                                                       _i32p, _i64p, _i32p, _i32p]
+    lib.mi_ba_absolute_pose_lds_capacity.argtypes = []
+    lib.mi_ba_absolute_pose_lds_capacity.restype = C.c_int32
     _lib = lib
     return lib
 
@@ -1538,6 +1578,94 @@ def triangulate_points(proj_matrix1=None, proj_matrix2=None, points1=None, point
                                           _ptr(c1, _dp), _ptr(c2, _dp), device, _ptr(out, _dp), _ptr(angles, _dp)),
           "mi_ba_triangulate_points")
     return out, angles
+
+
+def default_absolute_pose_estimation_options(**kw) -> AbsolutePoseEstimationOptions:
+    return _defaults(AbsolutePoseEstimationOptions, "mi_ba_default_absolute_pose_estimation_options", kw)
+
+
+def absolute_pose_lds_capacity() -> int:
+    return int(load().mi_ba_absolute_pose_lds_capacity())
+
+
+@dataclass
+class AbsolutePoseEstimationProblem:
+    """One focal-length hypothesis of EstimateAbsolutePose (estimators/pose.cc:50-75):
+    a correspondence set of the batch under a camera of the batch."""
+    set_index: int
+    camera_index: int
+    focal_length_factor: float = 1.0
+    seed: Optional[int] = None                      # None: the option's
+
+
+@dataclass
+class AbsolutePoseEstimationResult:
+    success: np.ndarray                  # [n] 0 / 1
+    proj_matrix: np.ndarray              # [n][3][4]; NaN for a failed problem
+    qvec: np.ndarray                     # [n][4]
+    tvec: np.ndarray                     # [n][3]
+    inlier_mask: list                    # [n] bool arrays; all False for a failed problem
+    num_trials: np.ndarray               # [n]
+    num_inliers: np.ndarray              # [n]
+    best_is_local: np.ndarray            # [n]
+
+
+class _AbsolutePoseEstimationArrays:
+    """The struct of arrays of correspondence sets [(points2D [m][2], points3D
+    [m][3])], cameras [(model id, params)] and a list of
+    AbsolutePoseEstimationProblem (kept alive beside the ctypes struct)."""
+
+    def __init__(self, sets, cameras, problems, options):
+        self.n = len(problems)
+        p2 = [np.asarray(a, np.float64).reshape(-1, 2) for a, _ in sets]
+        p3 = [np.asarray(b, np.float64).reshape(-1, 3) for _, b in sets]
+        for a, b in zip(p2, p3):
+            if len(a) != len(b):
+                raise ValueError("points2D and points3D differ in length")
+        self.set_off = _offsets([len(a) for a in p2])
+        self.points2D, self.points3D = _rows(p2, 2), _rows(p3, 3)
+        self.models = np.ascontiguousarray(np.array([m for m, _ in cameras], np.int32).reshape(-1))
+        prm = [np.asarray(c, np.float64).reshape(-1) for _, c in cameras]
+        self.prm_off = _offsets([len(c) for c in prm])
+        self.prm = np.ascontiguousarray(np.concatenate(prm)) if prm else np.zeros(0)
+        self.set_index = np.array([p.set_index for p in problems], np.int32)
+        self.camera_index = np.array([p.camera_index for p in problems], np.int32)
+        self.factor = np.array([p.focal_length_factor for p in problems], np.float64)
+        self.seed = np.array([int(options.seed) if p.seed is None else int(p.seed) for p in problems], np.uint64)
+        self.sizes = [int(self.set_off[i + 1] - self.set_off[i]) if 0 <= i < len(p2) else 0 for i in self.set_index]
+        self.mask_off = _offsets(self.sizes)
+        b = self.batch = AbsolutePoseEstimationBatch()
+        b.num_sets = len(p2)
+        b.set_offsets = _ptr(self.set_off, _i64p)
+        b.points2D = _ptr(self.points2D, _dp)
+        b.points3D = _ptr(self.points3D, _dp)
+        b.num_cameras = len(self.models)
+        b.camera_model_ids = _ptr(self.models, _i32p)
+        b.camera_param_offsets = _ptr(self.prm_off, _i64p)
+        b.camera_params = _ptr(self.prm, _dp)
+        b.num_problems = self.n
+        b.set_index = _ptr(self.set_index, _i32p)
+        b.camera_index = _ptr(self.camera_index, _i32p)
+        b.focal_length_factor = _ptr(self.factor, _dp)
+        b.seed = _ptr(self.seed, _u64p)
+
+
+def estimate_absolute_pose_batch(options: AbsolutePoseEstimationOptions, sets, cameras,
+                                 problems) -> AbsolutePoseEstimationResult:
+    """mi_ba_estimate_absolute_pose_batch: the LO-RANSAC of EstimateAbsolutePose
+    for every problem of the list in one launch."""
+    a = _AbsolutePoseEstimationArrays(sets, cameras, problems, options)
+    n, total = a.n, int(a.mask_off[-1])
+    P, q, t = np.full((n, 3, 4), np.nan), np.full((n, 4), np.nan), np.full((n, 3), np.nan)
+    mask = np.zeros(max(total, 1), np.uint8)
+    success, inl, local = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    trials = np.zeros(n, np.int64)
+    check(load().mi_ba_estimate_absolute_pose_batch(C.byref(options), C.byref(a.batch), _ptr(P, _dp), _ptr(q, _dp),
+                                                    _ptr(t, _dp), _ptr(mask, _u8p), _ptr(success, _i32p),
+                                                    _ptr(trials, _i64p), _ptr(inl, _i32p), _ptr(local, _i32p)),
+          "mi_ba_estimate_absolute_pose_batch")
+    masks = [mask[a.mask_off[k]:a.mask_off[k + 1]].astype(bool) for k in range(n)]
+    return AbsolutePoseEstimationResult(success, P, q, t, masks, trials, inl, local)
 
 
 def pose_problem_scene(problem: PoseProblem) -> Scene:
